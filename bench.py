@@ -31,6 +31,9 @@ the pose-gradient block per step), `video_1234_step` (one window step), `video_1
 `--gpus N` without a torch.distributed environment starts the N ranks itself
 (`python -m torch.distributed.run`, as a child process, before anything touches the
 GPU) and relays rank 0's line.
+
+`--dump-outputs DIR` writes what the last timed step returned (rank 0's frame) as DIR/<name>.npy; with the same
+arguments the inputs are the same in every run (seeded scene, weights and jitter), so two builds compare output for output.
 """
 import argparse
 import json
@@ -649,6 +652,21 @@ def spawn_rccl_leg(quick=False, timeout=900):
     return {'error': 'no result line (exit %d)' % r.returncode, 'stderr_tail': r.stderr[-1500:]}
 
 
+DUMP_CDF_ROWS = 16384      # rays of cdf_fine [B, 64] kept by --dump-outputs (the whole tensor alone is 64 MB)
+
+
+def dump_outputs(out_dir, out):
+    """--dump-outputs: the arrays the timed step returned to its caller (NeuSRenderer.render), as float32 .npy files, about
+    10 MB in all.  cdf_fine is kept on a fixed, seeded sample of DUMP_CDF_ROWS rays (cdf_fine_rays.npy: their indices)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+    rows = np.sort(np.random.default_rng(0).choice(arrays['cdf_fine'].shape[0], DUMP_CDF_ROWS, replace=False))
+    arrays['cdf_fine'] = arrays['cdf_fine'][rows]
+    arrays['cdf_fine_rays'] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -668,7 +686,11 @@ def main():
     ap.add_argument('--rccl-one-rank', action='store_true', help='run ONLY the one-rank RCCL leg (a process group of one rank over nccl on this GPU, the '
                     'sharded loops with their collectives forced) and print its JSON line')
     ap.add_argument('--no-rccl-leg', action='store_true', help='--gpus 1: skip the one-rank RCCL leg (run as a child process before the measurements)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (rank 0\'s frame) as DIR/<name>.npy, for output-by-output comparison of two builds')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.rccl_one_rank:
         sys.exit(rccl_one_rank_leg(args.fit_quick))
 
@@ -766,6 +788,8 @@ def main():
         dt = float(tt.item())
     samples_per_step = B * N_SAMPLES
     value = world * samples_per_step * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)       # before the secondary legs below reuse `out`
 
     # ---- the fitting loops: every leg that has a collective runs HERE, on all ranks; after it the process group is torn down and
     #      rank 0 alone takes the secondary measurements (no rank waits in a collective while rank 0 times a CPU oracle)
