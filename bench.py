@@ -11,9 +11,11 @@ everything already resident in HBM.  With --gpus N (launched by torch.distribute
 one rank per GPU) every rank renders its own frame (frame-sharded, no data-path
 collective): weak scaling, value = all ranks' ray-samples / max-over-ranks time.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (dominant kernel: the fused
-hand field kernel, MFMA-bound), `cpu_baseline` (the CPU oracle -- a port of the
-reference's PyTorch path -- timed on this box's host cores on a bounded crop) and
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints
+the headline with `roofline` (dominant kernel: the fused hand field kernel, MFMA-bound, timed inside the timed steps).
+`--full` adds every secondary measurement, each a run of its own after the timed steps: `roofline`'s separate
+kernel pass and sustained-MFMA probe, `value_culled` / `value_compact` / `f16_mode`, `c1`, `cpu_baseline` (the CPU
+oracle -- a port of the reference's PyTorch path -- timed on the host's cores on a bounded crop), `training`, and
 `fitting`: the second half of BASELINE's metric, frames/sec of the pose-fitting loops
 (configs[2..4]) on FIXED workloads at every N: `single_1` / `single_12` one
 optimisation step of fitting_single (C3: 196 rays x 192 shared depths, both fields, forward +
@@ -30,7 +32,8 @@ the pose-gradient block per step), `video_1234_step` (one window step), `video_1
 
 `--gpus N` without a torch.distributed environment starts the N ranks itself
 (`python -m torch.distributed.run`, as a child process, before anything touches the
-GPU) and relays rank 0's line.
+GPU) and relays rank 0's line.  `--full --gpus 1` also runs the one-rank RCCL leg (`--rccl-one-rank`) as a child
+process first.
 
 `--dump-outputs DIR` writes what the last timed step returned (rank 0's frame) as DIR/<name>.npy; with the same
 arguments the inputs are the same in every run (seeded scene, weights and jitter), so two builds compare output for output.
@@ -672,6 +675,8 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--full', action='store_true', help='also take every secondary measurement after the timed steps (with --gpus 1 the '
+                    'one-rank RCCL leg before them); the --no-* and --fit-* options below select among them.  A plain run measures the headline alone')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-crop', type=int, default=96)
     ap.add_argument('--no-culled', action='store_true', help='skip the secondary culled measurement')
@@ -706,7 +711,7 @@ def main():
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     rccl_leg = None
-    if world == 1 and not args.no_fitting and not args.no_rccl_leg and args.precision == 'f16x3':
+    if args.full and world == 1 and not args.no_fitting and not args.no_rccl_leg and args.precision == 'f16x3':
         rccl_leg = spawn_rccl_leg(args.fit_quick)          # a child process, before this process touches the GPU
     # HONERF_BENCH_SHARE_GPU=1: all ranks on device 0 with the gloo backend -- a functional check of the N > 1 code path
     # (sharding, the pose-gradient all-reduce between backward and Adam) on a box with ONE GPU; its timings mean nothing.
@@ -794,7 +799,7 @@ def main():
     # ---- the fitting loops: every leg that has a collective runs HERE, on all ranks; after it the process group is torn down and
     #      rank 0 alone takes the secondary measurements (no rank waits in a collective while rank 0 times a CPU oracle)
     fitting, single = None, None
-    if not args.no_fitting and args.precision == 'f16x3':
+    if args.full and not args.no_fitting and args.precision == 'f16x3':
         fitting, single = time_fit(dev, dist, rank, world, args.precision, args.fit_steps, 10, args.fit_outer, quick=args.fit_quick)
     if dist is not None:
         dist.barrier()
@@ -803,42 +808,45 @@ def main():
     if rank != 0:
         return
 
-    # ---- dominant kernel alone (k_field_hand<true>), HIP events on the launch stream ----------
+    # ---- dominant kernel alone (k_field_hand<true>), HIP events on the launch stream: with --full, or in place of the in-loop
+    #      timer when that did not see one launch per timed step ----------
     field = ren.field()
-    z = ren.last_z_vals
-    pts = torch.empty(B * N_SAMPLES, 3, device=dev)
-    dists = torch.empty(B * N_SAMPLES, device=dev)
-    L.check(lib.hn_sample_points(L.ptr(rays_o), L.ptr(rays_d), L.ptr(z), B, N_SAMPLES, 1, (FAR - NEAR) / N_SAMPLES,
-                                 L.ptr(pts), L.ptr(dists), L.stream_ptr()), 'hn_sample_points')
     n = B * N_SAMPLES
-    o_sdf, o_grad, o_rgb = torch.empty(n, device=dev), torch.empty(n, 3, device=dev), torch.empty(n, 3, device=dev)
-    ws_bytes = lib.hn_field_workspace_bytes(field.handle, n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    bt, tp = sc['bt_inv'].reshape(1, 21, 4, 4).contiguous(), sc['T_pose'].reshape(1, 21, 3).contiguous()
+    kernel_ms_separate = None
+    if args.full or k_count.value != args.steps:
+        z = ren.last_z_vals
+        pts = torch.empty(B * N_SAMPLES, 3, device=dev)
+        dists = torch.empty(B * N_SAMPLES, device=dev)
+        L.check(lib.hn_sample_points(L.ptr(rays_o), L.ptr(rays_d), L.ptr(z), B, N_SAMPLES, 1, (FAR - NEAR) / N_SAMPLES,
+                                     L.ptr(pts), L.ptr(dists), L.stream_ptr()), 'hn_sample_points')
+        o_sdf, o_grad, o_rgb = torch.empty(n, device=dev), torch.empty(n, 3, device=dev), torch.empty(n, 3, device=dev)
+        ws_bytes = lib.hn_field_workspace_bytes(field.handle, n)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        bt, tp = sc['bt_inv'].reshape(1, 21, 4, 4).contiguous(), sc['T_pose'].reshape(1, 21, 3).contiguous()
 
-    def field_launch():
-        L.check(lib.hn_field_eval(field.handle, L.ptr(pts), L.ptr(rays_d), n, N_SAMPLES, L.ptr(bt), L.ptr(tp), 1, n,
-                                  L.ptr(o_sdf), L.ptr(o_grad), L.ptr(o_rgb), None, L.ptr(ws), ws_bytes, L.stream_ptr()),
-                'hn_field_eval')
+        def field_launch():
+            L.check(lib.hn_field_eval(field.handle, L.ptr(pts), L.ptr(rays_d), n, N_SAMPLES, L.ptr(bt), L.ptr(tp), 1, n,
+                                      L.ptr(o_sdf), L.ptr(o_grad), L.ptr(o_rgb), None, L.ptr(ws), ws_bytes, L.stream_ptr()),
+                    'hn_field_eval')
 
-    field_launch()
-    torch.cuda.synchronize()
-    k_launches = max(1, min(args.steps, 3))
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(k_launches):
         field_launch()
-    e1.record()
-    torch.cuda.synchronize()
-    kernel_ms_separate = e0.elapsed_time(e1) / k_launches
+        torch.cuda.synchronize()
+        k_launches = max(1, min(args.steps, 3))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(k_launches):
+            field_launch()
+        e1.record()
+        torch.cuda.synchronize()
+        kernel_ms_separate = e0.elapsed_time(e1) / k_launches
     # `roofline` is priced on the launches of the TIMED steps (above); the separate pass -- the same launch alone, after the fitting
-    # legs have heated the part -- stays in the line as a cross-check
+    # legs have heated the part -- stays in the --full line as a cross-check
     kernel_ms = kernel_ms_in_loop if k_count.value == args.steps else kernel_ms_separate
     achieved = n * HAND_FLOP_PER_SAMPLE / (kernel_ms * 1e-3) / 1e12
     # ---- secondary figure: the same step with the exact far-field early-out enabled ("may additionally
     #      be reported culled"); `value` above stays the dense number
     culled = None
-    if args.precision == 'f16x3' and not args.no_culled:
+    if args.full and args.precision == 'f16x3' and not args.no_culled:
         field.set_culling(True)
         step()
         torch.cuda.synchronize()
@@ -851,7 +859,7 @@ def main():
     # ---- secondary figure: the same step with the exact sample-level far-field skip (hn_field_set_compaction: the field runs on
     #      the compacted list of the samples that have a live bone mask; bit-identical output).  Never the headline.
     compact = None
-    if args.precision == 'f16x3' and not args.no_culled:
+    if args.full and args.precision == 'f16x3' and not args.no_culled:
         field.set_compaction(True)
         step()
         torch.cuda.synchronize()
@@ -866,7 +874,7 @@ def main():
     # ---- secondary figure (BASELINE configs[1] names "bf16"): the same step with precision = 'f16' -- hidden SDF layers and
     #      reverse sweep on ONE f16 MFMA per product (HN_PREC_F16) -- with its measured difference from the headline frame
     f16 = None
-    if args.precision == 'f16x3' and not args.no_f16:
+    if args.full and args.precision == 'f16x3' and not args.no_f16:
         ref_col, ref_ws = out['color_fine'].clone(), out['weight_sum'].clone()
         ren.precision = 'f16'
         o16 = step()
@@ -922,7 +930,7 @@ def main():
         if not args.no_cpu_baseline:
             fitting['cpu_baseline'] = cpu_fit_baseline(single)
     training = None
-    if not args.no_training and args.precision == 'f16x3':
+    if args.full and not args.no_training and args.precision == 'f16x3':
         # one iteration of exp_runner.train (render, loss, backward into every network parameter, Adam,
         # re-pack) at the reference's batch (confs: 441 rays, 64 + 64 samples); secondary to the headline
         sys.path.insert(0, os.path.join(ROOT, 'tools'))
@@ -930,12 +938,12 @@ def main():
         training = {k: train_step_bench.measure(k, dev, 441, 10, 3, args.precision) for k in ('obj', 'hand')}
         # secondary: the hand iteration with every sample evaluated (the product's default aggregates the far field exactly)
         training['hand_dense'] = train_step_bench.measure('hand', dev, 441, 10, 3, args.precision, compact=False)
-    c1 = time_c1(dev, args.precision, not args.no_cpu_baseline) if not args.no_c1 else None
+    c1 = time_c1(dev, args.precision, not args.no_cpu_baseline) if args.full and not args.no_c1 else None
     # ---- the rate the matrix pipe SUSTAINS on this box (hn_debug_mfma_probe: a kernel of nothing but f16 MFMAs on random
     #      operands, ~0.2 s per launch so that the power controller settles): the chip is power-limited well below the
     #      guide's 2.4 GHz figure, so the roofline entry states the fraction of this measured rate beside the nominal one
     sustained = None
-    if args.precision == 'f16x3' and not share:
+    if args.full and args.precision == 'f16x3' and not share:
         import ctypes
         flop = ctypes.c_double(0.0)
         iters = 300000
@@ -987,7 +995,7 @@ def main():
     if compact is not None:
         res['value_compact'] = compact['value']   # rank 0's frame, sample-level far-field skip on (bit-identical output)
         res['compact_bit_identical_to_dense'] = compact['bit_identical_to_dense']
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         res['cpu_baseline'] = cpu_baseline(sdf, col, sc, args.cpu_crop)
     print(json.dumps(res))
 

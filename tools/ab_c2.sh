@@ -6,7 +6,7 @@ cd $R
 for rep in 1 2; do
 for L in "$@"; do
   export HONERF_LIB=$R/ho-nerf_amd/$L
-  python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-culled --no-fitting --no-training --no-c1 --no-f16 2>/dev/null | python3 -c "
+  python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-culled --no-fitting --no-training --no-c1 --no-f16 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.readline())
 r = d['roofline']

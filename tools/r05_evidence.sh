@@ -41,9 +41,9 @@ timeout 300 python tools/seq_repro_diag.py --frames 6 --runs 4 --check --no-defe
 timeout 300 python tools/host_time_probe.py > $O/host_time_probe.txt 2>&1
 for f in 1 2 4 8; do timeout 200 python tools/fit_profile.py 60 halo pipe $f 2>&1 | tail -1 >> $O/frames_side_by_side.txt; done
 (HN_TAPED_GRID=cus timeout 200 python tools/fit_profile.py 60 halo pipe 4 2>&1 | tail -1 | sed 's/^/persistent grids (HN_TAPED_GRID=cus): /' >> $O/frames_side_by_side.txt)
-(timeout 1500 python bench.py > $O/bench_line.json 2> $O/bench_err.log; echo "bench exit $?" >> $O/bench_err.log)
+(timeout 1500 python bench.py --full > $O/bench_line.json 2> $O/bench_err.log; echo "bench exit $?" >> $O/bench_err.log)
 # the N > 1 code path, functionally: two gloo ranks on this one GPU (timings mean nothing)
-(HONERF_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --steps 2 --warmup 1 --fit-quick --no-cpu-baseline --no-culled --no-f16 --no-c1 --no-training > $O/bench_2ranks_one_gpu_gloo_functional.json 2> $O/bench_2ranks_err.log; echo "2-rank exit $?" >> $O/bench_2ranks_err.log)
+(HONERF_BENCH_SHARE_GPU=1 timeout 900 python bench.py --full --gpus 2 --steps 2 --warmup 1 --fit-quick --no-cpu-baseline --no-culled --no-f16 --no-c1 --no-training > $O/bench_2ranks_one_gpu_gloo_functional.json 2> $O/bench_2ranks_err.log; echo "2-rank exit $?" >> $O/bench_2ranks_err.log)
 tail -2 $O/bench_2ranks_err.log
 tail -c 1200 $O/bench_line.json
 tail -2 $O/bench_err.log
