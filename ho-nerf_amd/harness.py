@@ -51,3 +51,52 @@ def render_image(renderer, camera, H, W, near, far, bt_inv, T_pose_21, Ro=None, 
                                     Ro.T.contiguous(), To, index, **kw))
     merged = {k: torch.cat([o[k] for o in outs], 0) for k in ('color_fine', 'weight_sum', 'weight_max')}
     return to_image(merged['color_fine'], H, W), merged
+
+
+# ---- mesh export: the `mesh_*/{cid}_hand.ply` / `_obj.ply` files of get_res.py, without a mesh library --------------------------
+_PLY_HEADER = ('ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n'
+               'element face %d\nproperty list uchar int vertex_indices\nend_header\n')
+_PLY_FACE = np.dtype([('n', 'u1'), ('v', '<i4', (3,))])
+
+
+def write_ply(path, vertices, triangles):
+    """Binary little-endian PLY: float32 vertex x / y / z, faces as uchar-count int32 lists (what open3d and trimesh read).
+    vertices [V,3], triangles [T,3] (numpy or tensors)."""
+    v = np.ascontiguousarray(_host(vertices), dtype='<f4').reshape(-1, 3)
+    t = _host(triangles).reshape(-1, 3)
+    if t.size and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError('write_ply: triangle indices outside [0, %d)' % len(v))
+    faces = np.empty(len(t), dtype=_PLY_FACE)
+    faces['n'] = 3
+    faces['v'] = t
+    with open(path, 'wb') as f:
+        f.write((_PLY_HEADER % (len(v), len(t))).encode('ascii'))
+        f.write(v.tobytes())
+        f.write(faces.tobytes())
+
+
+def read_ply(path):
+    """The files write_ply writes -> (vertices float32 [V,3], triangles int64 [T,3])."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    end = data.find(b'end_header\n')
+    if not data.startswith(b'ply\n') or end < 0:
+        raise ValueError('%s: not a PLY file' % path)
+    counts = {}
+    for line in data[:end].decode('ascii').splitlines():
+        w = line.split()
+        if w[:1] == ['format'] and w[1] != 'binary_little_endian':
+            raise ValueError('%s: only binary_little_endian PLY is read' % path)
+        if w[:1] == ['element']:
+            counts[w[1]] = int(w[2])
+    nv, nf = counts.get('vertex', 0), counts.get('face', 0)
+    body = end + len(b'end_header\n')
+    v = np.frombuffer(data, dtype='<f4', count=3 * nv, offset=body).reshape(nv, 3).copy()
+    faces = np.frombuffer(data, dtype=_PLY_FACE, count=nf, offset=body + 12 * nv)
+    if nf and (faces['n'] != 3).any():
+        raise ValueError('%s: only triangle faces are read' % path)
+    return v, faces['v'].astype(np.int64).reshape(nf, 3)
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)

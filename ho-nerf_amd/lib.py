@@ -161,6 +161,9 @@ SIGNATURES = {
                              c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_sz, c_vp, c_sz, c_i, c_vp]),
     'hn_side_stream': (c_i, [ctypes.POINTER(c_vp)]),
     'hn_stream_wait': (c_i, [c_vp, c_vp]),
+    'hn_mcubes_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
+    'hn_mcubes_count': (c_i, [c_f, c_i, c_i, c_i, c_fl, c_vp, c_vp, c_sz, c_vp]),
+    'hn_mcubes_emit': (c_i, [c_f, c_i, c_i, c_i, c_fl, c_vp, c_sz, ctypes.c_longlong, ctypes.c_longlong, c_f, c_vp, c_vp]),
 }
 
 _lib = None

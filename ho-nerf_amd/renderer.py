@@ -130,8 +130,23 @@ def _marching_cubes(u, threshold, resolution, b_min_np, b_max_np):
                           'extract_fields() returns the SDF volume without it') from e
     vertices, triangles = mcubes.marching_cubes(u, threshold)
     triangles = triangles[..., ::-1]
-    vertices = vertices / (resolution - 1.0) * (b_max_np - b_min_np)[None, :] + b_min_np[None, :]
-    return vertices, triangles
+    return _to_world(vertices, resolution, b_min_np, b_max_np), triangles
+
+
+def _to_world(vertices, resolution, b_min_np, b_max_np):
+    """utils/renderer.py:283: index space -> the box of the grid (float64, as the reference's vertices are)."""
+    return vertices / (resolution - 1.0) * (b_max_np - b_min_np)[None, :] + b_min_np[None, :]
+
+
+def _mesh(volume_fn, threshold, resolution, b_min_np, b_max_np, mesher):
+    """The marching cubes step of extract_geometry.  mesher=None: PyMCubes on the host volume, as the reference;
+    'native': hn_mcubes on the very device volume extract_fields copies out (orientation emitted outward, not flipped again)
+    -> numpy float64 vertices [V,3], int64 triangles [T,3]."""
+    if mesher is None:
+        return _marching_cubes(volume_fn().cpu().numpy(), threshold, resolution, b_min_np, b_max_np)
+    from .mesh import marching_cubes
+    v, t = marching_cubes(volume_fn(), threshold)
+    return _to_world(v.cpu().numpy().astype(np.float64), resolution, b_min_np, b_max_np), t.cpu().numpy()
 
 
 def _wants_grad(*xs):
@@ -304,20 +319,27 @@ class NeuSRenderer:
             'gradient_error': (gerr / float(B * S)).reshape(()),
         }
 
-    def extract_fields(self, bound_min, bound_max, resolution, bt_inv=None, T_pose_21=None):
-        """The SDF volume u [res,res,res] of extract_geometry (utils/renderer.py:260-278): the reference walks the grid
-        in 64^3 host chunks, here the whole grid is one hn_field_sdf launch."""
+    def _volume(self, bound_min, bound_max, resolution, bt_inv=None, T_pose_21=None):
+        """extract_fields' volume as a device tensor [res,res,res]."""
         dev = torch.device('cuda')
         pts, _, _ = _grid_points(bound_min, bound_max, resolution, dev)
         with torch.no_grad():
             val = self.field().sdf(pts, bt_inv, T_pose_21)
-        return val.reshape(resolution, resolution, resolution).cpu().numpy()
+        return val.reshape(resolution, resolution, resolution)
 
-    def extract_geometry(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, threshold=0.0):
-        """utils/renderer.py:260-284 -> (vertices, triangles)."""
+    def extract_fields(self, bound_min, bound_max, resolution, bt_inv=None, T_pose_21=None):
+        """The SDF volume u [res,res,res] of extract_geometry (utils/renderer.py:260-278): the reference walks the grid
+        in 64^3 host chunks, here the whole grid is one hn_field_sdf launch."""
+        return self._volume(bound_min, bound_max, resolution, bt_inv, T_pose_21).cpu().numpy()
+
+    def extract_geometry(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, threshold=0.0, *, mesher=None):
+        """utils/renderer.py:260-284 -> (vertices, triangles).  mesher=None: PyMCubes, as the reference; 'native': the device
+        mesher (honerf_amd.mesh) on the same volume."""
         _, bmin, bmax = _grid_points(bound_min, bound_max, 2, torch.device('cpu'))
-        u = self.extract_fields(bound_min, bound_max, resolution, bt_inv, T_pose_21)
-        return _marching_cubes(u, threshold, resolution, bmin, bmax)
+        if mesher not in (None, 'native'):
+            raise ValueError("extract_geometry: mesher must be None (PyMCubes) or 'native', got %r" % (mesher,))
+        return _mesh(lambda: self._volume(bound_min, bound_max, resolution, bt_inv, T_pose_21), threshold, resolution, bmin, bmax,
+                     mesher)
 
 
 class NeuSRenderer_fitting:
@@ -500,6 +522,10 @@ class NeuSRenderer_fitting:
     def extract_fields(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type):
         """The SDF volume of extract_geometry (utils/renderer.py:537-556) in one launch; 'obj' queries go through
         o' = Ro (p - To) first (:550-552)."""
+        return self._volume(bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type).cpu().numpy()
+
+    def _volume(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type):
+        """extract_fields' volume as a device tensor [res,res,res]."""
         dev = torch.device('cuda')
         pts, _, _ = _grid_points(bound_min, bound_max, resolution, dev)
         hand, obj = self.fields()
@@ -513,13 +539,16 @@ class NeuSRenderer_fitting:
                 _lib.check(self.lib.hn_obj_local_fwd(_lib.ptr(pts), _lib.ptr(pts), _lib.ptr(Ro_), _lib.ptr(To_), 1, pts.shape[0],
                                                      _lib.ptr(local), _lib.ptr(dummy), _lib.stream_ptr()), 'hn_obj_local_fwd')
                 val = obj.sdf(local)
-        return val.reshape(resolution, resolution, resolution).cpu().numpy()
+        return val.reshape(resolution, resolution, resolution)
 
-    def extract_geometry(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type, threshold=0.0):
-        """utils/renderer.py:537-564 -> (vertices, triangles)."""
+    def extract_geometry(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type, threshold=0.0, *, mesher=None):
+        """utils/renderer.py:537-564 -> (vertices, triangles).  mesher=None: PyMCubes, as the reference; 'native': the device
+        mesher (honerf_amd.mesh) on the same volume."""
         _, bmin, bmax = _grid_points(bound_min, bound_max, 2, torch.device('cpu'))
-        u = self.extract_fields(bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type)
-        return _marching_cubes(u, threshold, resolution, bmin, bmax)
+        if mesher not in (None, 'native'):
+            raise ValueError("extract_geometry: mesher must be None (PyMCubes) or 'native', got %r" % (mesher,))
+        return _mesh(lambda: self._volume(bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type), threshold, resolution,
+                     bmin, bmax, mesher)
 
     def get_inner_point_id(self, pts, bt_inv, T_pose_21):
         """utils/renderer.py:566-572: indices of points with hand sdf <= 0."""

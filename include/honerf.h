@@ -650,6 +650,24 @@ int hn_render_single_bwd_taped(const hn_field* f, const float* rays_o, const flo
                                float* g_rays_o, float* g_rays_d, float* g_bt_inv, float* g_T_pose, const void* tape, size_t tape_bytes,
                                void* workspace, size_t workspace_bytes, hn_stream_t stream);
 
+/* ---- marching cubes (hn_mcubes.hip): what utils/renderer.py:279-284 (and :561-564) hands to PyMCubes, on the device --------------
+ * volume [nx, ny, nz] fp32 (x slowest, the 'ij' grid of extract_geometry; 16-byte aligned), every dim >= 2 and 3 nx ny nz < 2^31.
+ * A grid point is inside when its value < threshold.  Every grid edge that crosses gets exactly one vertex, shared by the cells
+ * around it, at v0 + t (v1 - v0), t = (threshold - v0) / (v1 - v0), in index space; vertices are ordered by the owning point
+ * (the edge's lower end) and then axis x, y, z; triangles by cell and then their place in the classic 256-case table, with the
+ * normal (v1 - v0) x (v2 - v0) toward increasing value (outward for an SDF: what the reference gets from triangles[..., ::-1]).
+ * The output is the same bits on every run.
+ *   hn_mcubes_workspace_bytes: the workspace both calls take (0 for dims the mesher refuses);
+ *   hn_mcubes_count: counts -> totals [2] int64 DEVICE = {V, T} (the caller reads them back, 16 bytes, and sizes the outputs);
+ *     the workspace keeps the offsets the emit call needs;
+ *   hn_mcubes_emit: on the workspace of the count call of the same volume and threshold (same stream) -> vertices [V, 3] fp32,
+ *     triangles [T, 3] int64.  V = 0 or T = 0 launches nothing. */
+size_t hn_mcubes_workspace_bytes(int nx, int ny, int nz);
+int hn_mcubes_count(const float* volume, int nx, int ny, int nz, float threshold, long long* totals, void* workspace, size_t workspace_bytes,
+                    hn_stream_t stream);
+int hn_mcubes_emit(const float* volume, int nx, int ny, int nz, float threshold, void* workspace, size_t workspace_bytes, long long n_verts,
+                   long long n_tris, float* vertices, long long* triangles, hn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
