@@ -164,6 +164,12 @@ SIGNATURES = {
     'hn_mcubes_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
     'hn_mcubes_count': (c_i, [c_f, c_i, c_i, c_i, c_fl, c_vp, c_vp, c_sz, c_vp]),
     'hn_mcubes_emit': (c_i, [c_f, c_i, c_i, c_i, c_fl, c_vp, c_sz, ctypes.c_longlong, ctypes.c_longlong, c_f, c_vp, c_vp]),
+    'hn_voxelize_workspace_bytes': (c_sz, [ctypes.c_longlong]),
+    'hn_voxelize_count': (c_i, [c_vp, ctypes.c_longlong, c_db, ctypes.POINTER(ctypes.c_longlong), c_vp, c_sz, c_vp]),
+    'hn_voxelize_emit': (c_i, [c_vp, ctypes.c_longlong, c_db, c_vp, c_sz, ctypes.c_longlong, c_vp, c_vp]),
+    'hn_interact_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong]),
+    'hn_winding_contains': (c_i, [c_f, ctypes.c_longlong, c_f, ctypes.c_longlong, c_f, c_vp, c_f, c_vp, c_sz, c_vp]),
+    'hn_closest_distance': (c_i, [c_f, ctypes.c_longlong, c_f, ctypes.c_longlong, c_f, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

@@ -668,6 +668,37 @@ int hn_mcubes_count(const float* volume, int nx, int ny, int nz, float threshold
 int hn_mcubes_emit(const float* volume, int nx, int ny, int nz, float threshold, void* workspace, size_t workspace_bytes, long long n_verts,
                    long long n_tris, float* vertices, long long* triangles, hn_stream_t stream);
 
+/* ---- hand-object interaction (hn_interact.hip): what analys_results/analys_interaction.py:14-19 and :44-55 ask trimesh for -----
+ * Meshes are rows of 9 coordinates per triangle (a, b, c), world metres.
+ * Voxelization (Trimesh.voxelized(pitch), subdivide, max_iter 10), fp64: a triangle with an edge length sqrt((dx^2 + dy^2) + dz^2)
+ * > pitch / 2 is split 4-way at its edge midpoints (a + b) / 2, each child judged again, at most 10 rounds; every vertex of every
+ * leaf gives the key k = rint(v / pitch) per axis, packed as ((kx + 2^20) << 42) | ((ky + 2^20) << 21) | (kz + 2^20).  Keys are
+ * not deduplicated: each leaf writes its 3 in the order of a depth-first walk, triangle by triangle.
+ *   hn_voxelize_workspace_bytes: the workspace both calls take (0 for n_tris outside [0, 2^31 - 256));
+ *   hn_voxelize_count: counts and reads back the total (waits for the stream) -> *n_keys HOST.  Returns HN_EINVAL with a message
+ *     when a triangle would need an 11th round or has a vertex with |v / pitch| >= 2^20 - 1 (its key would not fit): then the
+ *     workspace does not hold offsets for an emit call;
+ *   hn_voxelize_emit: on the workspace of the count call of the same mesh and pitch (same stream) -> keys [n_keys] int64.
+ * Containment (Trimesh.contains), fp32: inside <=> |w| > 1/2, w the generalized winding number (sum over the triangles of the Van
+ * Oosterom-Strackee solid angle 2 atan2(det, den), over 4 pi); a point outside bbox {xmin, ymin, zmin, xmax, ymax, zmax} (DEVICE,
+ * the mesh's bounds) is outside without evaluation.  Distance (trimesh.proximity.closest_point), fp32: the exact unsigned distance
+ * to the nearest triangle.  Both are summed / minimised in a fixed order without atomics: the same bits on every run.
+ *   hn_interact_workspace_bytes: the workspace of one hn_winding_contains / hn_closest_distance call (0 for counts outside
+ *     [0, 2^31 - 256));
+ *   hn_winding_contains: points [P, 3] fp32 -> inside [P] uint8 (0 / 1), winding [P] fp32 (w; may be NULL);
+ *   hn_closest_distance: points [P, 3] fp32 -> dist [P] fp32.
+ *   P = 0 or T = 0 launches nothing and leaves the outputs as they are. */
+size_t hn_voxelize_workspace_bytes(long long n_tris);
+int hn_voxelize_count(const double* tri_verts, long long n_tris, double pitch, long long* n_keys, void* workspace, size_t workspace_bytes,
+                      hn_stream_t stream);
+int hn_voxelize_emit(const double* tri_verts, long long n_tris, double pitch, void* workspace, size_t workspace_bytes, long long n_keys,
+                     long long* keys, hn_stream_t stream);
+size_t hn_interact_workspace_bytes(long long n_points, long long n_tris);
+int hn_winding_contains(const float* points, long long n_points, const float* tri_verts, long long n_tris, const float* bbox,
+                        unsigned char* inside, float* winding, void* workspace, size_t workspace_bytes, hn_stream_t stream);
+int hn_closest_distance(const float* points, long long n_points, const float* tri_verts, long long n_tris, float* dist, void* workspace,
+                        size_t workspace_bytes, hn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
