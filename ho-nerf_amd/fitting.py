@@ -1376,6 +1376,39 @@ def fit_frames_sharded(renderer, n_frames, make_frame, near, far, fit_type='12',
     return out
 
 
+class _PoseSaver:
+    """`pose_saver`'s callable: save(frame_id, pose_chain, terms), with `done(frame_id)` and `path(frame_id)` beside it."""
+
+    def __init__(self, directory, fit_type, gt, name):
+        self.directory = os.path.join(directory, 'pose_' + str(fit_type))
+        self.gt, self.name = gt, name
+
+    def path(self, frame_id):
+        return os.path.join(self.directory, '%s.pickle' % self.name(frame_id))
+
+    def done(self, frame_id):
+        return os.path.exists(self.path(frame_id))
+
+    def __call__(self, frame_id, pose_chain, terms=None):
+        from . import harness
+        with torch.no_grad():
+            pose = pose_chain()
+            pred = [pose[k][0].detach().float().cpu().numpy() for k in ('joint_3d', 'obj_r', 'obj_t')]
+        gt = self.gt(frame_id) if callable(self.gt) else self.gt[frame_id] if self.gt is not None else None
+        gts = {} if gt is None else {'gt_' + k: gt[k] for k in ('joint3d', 'Ro', 'To')}
+        os.makedirs(self.directory, exist_ok=True)
+        harness.write_pose(self.path(frame_id), *pred, **gts)
+
+
+def pose_saver(directory, fit_type, gt=None, name=str):
+    """The pose dump of fitting_single.py:293-315 as the `save` of `fit_frames_sharded`: evaluates the fitted chain (no gradient) and
+    writes directory/pose_<fit_type>/<name(frame_id)>.pickle (`harness.write_pose`) from joint_3d[0], obj_r, obj_t.  gt: the frame's
+    ground truth, {'joint3d', 'Ro', 'To'}, as a mapping frame_id -> dict or a callable (the gt_* keys of :164-166; left out when
+    None).  The returned callable has `done(frame_id)`, the existence of that file (:156-158), for `fit_frames_sharded(done=...)`,
+    and `path(frame_id)`."""
+    return _PoseSaver(directory, fit_type, gt, name)
+
+
 def synthetic_views(n_views, n_frames, rays_per_frame, seed, joints_center, device='cuda', H=230, W=266):
     """Synthetic stand-in for one fit_*_dataset item (the data set is an external download): `n_views` ring cameras
     looking at the hand, per view `rays_per_frame` pixels per frame drawn from a synthetic mask (NDC convention of

@@ -6,6 +6,8 @@ rays (`_xy_to_ray_bundle`, utils/utils.py:31-115), split the rays into `batch_si
 reshaped `[H, W, 3]` (exp_runner.py:356-372).  Here the ray bundle comes from `hn_ray_gen` and one `render`
 call covers all H*W rays (chunking stays available for memory-bound hosts through `batch_size`).
 """
+import pickle
+
 import numpy as np
 import torch
 
@@ -100,3 +102,40 @@ def read_ply(path):
 
 def _host(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+# ---- pose files: the `pose_<fit_type>/<cid>.pickle` of fitting_single.py:164-166, 297-315, what analys_results/ reads ---------------
+_POSE_SHAPES = {'joint3d': (21, 3), 'Ro': (3, 3), 'To': (3,)}
+
+
+def write_pose(path, pred_joint3d, pred_Ro, pred_To, gt_joint3d=None, gt_Ro=None, gt_To=None):
+    """The reference's pose pickle: a dict of float32 numpy arrays pred_joint3d [21,3], pred_Ro [3,3], pred_To [3] and, when given
+    (all three or none), gt_joint3d, gt_Ro, gt_To.  Arrays or tensors; a leading frame axis of 1 is dropped."""
+    gts = (gt_joint3d, gt_Ro, gt_To)
+    if any(g is None for g in gts) and not all(g is None for g in gts):
+        raise ValueError('write_pose: gt_joint3d, gt_Ro and gt_To go together')
+    param = {}
+    for prefix, vals in (('pred', (pred_joint3d, pred_Ro, pred_To)), ('gt', gts)):
+        for (name, shape), a in zip(_POSE_SHAPES.items(), vals):
+            if a is None:
+                continue
+            a = np.array(_host(a), dtype=np.float32)
+            if a.shape == (1,) + shape:
+                a = a[0]
+            if a.shape != shape:
+                raise ValueError('write_pose: %s_%s has shape %s, expected %s' % (prefix, name, a.shape, shape))
+            param['%s_%s' % (prefix, name)] = np.ascontiguousarray(a)
+    with open(path, 'wb') as f:
+        pickle.dump(param, f)
+
+
+def read_pose(path):
+    """A pose pickle -> its dict of numpy arrays.  A file without pred_joint3d, pred_Ro and pred_To is refused."""
+    with open(path, 'rb') as f:
+        param = pickle.load(f)
+    need = ['pred_' + k for k in _POSE_SHAPES]
+    if not isinstance(param, dict) or any(k not in param for k in need):
+        have = sorted(param) if isinstance(param, dict) else type(param).__name__
+        raise ValueError('%s: not a pose file: %s missing (it holds %s)' % (path, ', '.join(k for k in need if not isinstance(param, dict)
+                                                                                                or k not in param), have))
+    return {k: np.asarray(v) for k, v in param.items()}

@@ -170,6 +170,12 @@ SIGNATURES = {
     'hn_interact_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong]),
     'hn_winding_contains': (c_i, [c_f, ctypes.c_longlong, c_f, ctypes.c_longlong, c_f, c_vp, c_f, c_vp, c_sz, c_vp]),
     'hn_closest_distance': (c_i, [c_f, ctypes.c_longlong, c_f, ctypes.c_longlong, c_f, c_vp, c_sz, c_vp]),
+    'hn_pm_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong]),
+    'hn_pm_transform': (c_i, [c_f, ctypes.c_longlong, c_f, c_f, c_f, ctypes.c_longlong, c_f, c_vp]),
+    'hn_pm_nearest': (c_i, [c_f, ctypes.c_longlong, c_f, ctypes.c_longlong, ctypes.c_longlong, c_f, c_vp, c_sz, c_vp]),
+    'hn_pm_paired': (c_i, [c_f, c_f, ctypes.c_longlong, ctypes.c_longlong, c_f, c_vp]),
+    'hn_pm_row_mean': (c_i, [c_f, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp]),
+    'hn_pm_accel': (c_i, [c_f, c_f, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp]),
 }
 
 _lib = None

@@ -699,6 +699,30 @@ int hn_winding_contains(const float* points, long long n_points, const float* tr
 int hn_closest_distance(const float* points, long long n_points, const float* tri_verts, long long n_tris, float* dist, void* workspace,
                         size_t workspace_bytes, hn_stream_t stream);
 
+/* ---- pose accuracy (hn_posemetric.hip): analys_results/analys_hand_obj_pose.py and analys_results/analys_acc_err.py on the device --
+ * Clouds are [F, N, 3] fp32, frame after frame.  Every count must be positive and frames x points below 2^31 - 1024; a refused
+ * count or a NULL pointer is HN_EINVAL with a message, never a fault.  Nothing synchronises or allocates; every reduction runs in
+ * a fixed order without atomics: the same bits on every run.
+ *   hn_pm_workspace_bytes: the workspace of one hn_pm_nearest call (0 for counts it refuses);
+ *   hn_pm_transform: verts [V, 3], R [F, 3, 3], t [F, 3], c [F, 3] -> out [F, V, 3] = R_f v + t_f - c_f, evaluated in fp64 and
+ *     rounded once (analys_hand_obj_pose.py:102-104 forms vert_model @ Ro.T + To in float64 from float32 poses; c_f = the
+ *     ground-truth translation keeps the stored coordinates object-sized);
+ *   hn_pm_nearest: queries [F, Nq, 3], targets [F, Nt, 3] -> dist [F, Nq], the Euclidean distance from each query to the nearest
+ *     target of its frame (the cKDTree query of adi, :21-25), from coordinate differences, one sqrt per query;
+ *   hn_pm_paired: a, b [F, N, 3] -> dist [F, N] = |a - b| row by row (add, :17-19; the vertex error :106; the joint error :97),
+ *     differences and norm in fp64, rounded once;
+ *   hn_pm_row_mean: x [F, N] fp32 -> mean [F] fp64, accumulated in fp64 (the .mean() of :18, :24, :97, :106);
+ *   hn_pm_accel: gt, pred [N, J, 3] -> accel [N - 2] fp64 = mean_j |(p[i] - 2 p[i+1] + p[i+2]) - (g[i] - 2 g[i+1] + g[i+2])|, the
+ *     differences in fp64 (compute_error_accel, analys_acc_err.py:35-38, :49, without the vis mask); N >= 3. */
+size_t hn_pm_workspace_bytes(long long n_frames, long long n_queries, long long n_targets);
+int hn_pm_transform(const float* verts, long long n_verts, const float* R, const float* t, const float* c, long long n_frames, float* out,
+                    hn_stream_t stream);
+int hn_pm_nearest(const float* queries, long long n_queries, const float* targets, long long n_targets, long long n_frames, float* dist,
+                  void* workspace, size_t workspace_bytes, hn_stream_t stream);
+int hn_pm_paired(const float* a, const float* b, long long n_frames, long long n_points, float* dist, hn_stream_t stream);
+int hn_pm_row_mean(const float* x, long long n_rows, long long n_cols, double* mean, hn_stream_t stream);
+int hn_pm_accel(const float* gt, const float* pred, long long n_frames, long long n_points, double* accel, hn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
