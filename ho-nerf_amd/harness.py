@@ -5,7 +5,11 @@ rays (`_xy_to_ray_bundle`, utils/utils.py:31-115), split the rays into `batch_si
 `renderer.render` per chunk, concatenate `color_fine`, and form the image as `(rgb * 255).clip(0, 255)`
 reshaped `[H, W, 3]` (exp_runner.py:356-372).  Here the ray bundle comes from `hn_ray_gen` and one `render`
 call covers all H*W rays (chunking stays available for memory-bound hosts through `batch_size`).
+
+`render_views` is the two-field counterpart, `get_res.py --render True` (get_res.py:246-287): the fitted hand and object from a set
+of held-out cameras, quantised on the device; `write_image` / `read_image` store such images without an image library.
 """
+import os
 import pickle
 
 import numpy as np
@@ -53,6 +57,100 @@ def render_image(renderer, camera, H, W, near, far, bt_inv, T_pose_21, Ro=None, 
                                     Ro.T.contiguous(), To, index, **kw))
     merged = {k: torch.cat([o[k] for o in outs], 0) for k in ('color_fine', 'weight_sum', 'weight_max')}
     return to_image(merged['color_fine'], H, W), merged
+
+
+def render_views(renderer, cameras, H, W, near, far, bt_inv, T_pose_21, Ro, To, batch_size=16384, t_rand=None):
+    """get_res.py:246-287 for a NeuSRenderer_fitting: every camera of `cameras` (a dict of R [V,3,3], T [V,3], focal [V,2], principal
+    [V,2], as synth.ring_cameras returns) -> uint8 [V, H, W, 3] on the device.
+
+    Per camera the full NDC grid goes through `image_rays` and then through `renderer.render(.., None, Ro.T, To)` in chunks of
+    `batch_size` rays under torch.no_grad() (:263-281; the chunks keep the per-sample outputs of a full image, about 1 GB at
+    512 x 334 x 192 samples, out of memory).  `color_fine` is quantised on the device exactly as `to_image` does on the host: fp32
+    * 255, clamp to [0, 255], truncate.  `t_rand` is [V, H*W, 1] (the stratified jitter, fixed for a reproducible render) or None."""
+    device = torch.device('cuda')
+    cams = {k: np.asarray(cameras[k], dtype=np.float32) for k in ('R', 'T', 'focal', 'principal')}
+    V = cams['R'].shape[0]
+    if cams['R'].shape != (V, 3, 3) or cams['T'].shape != (V, 3) or cams['focal'].shape != (V, 2) or cams['principal'].shape != (V, 2):
+        raise ValueError('render_views: cameras must hold R [V,3,3], T [V,3], focal [V,2], principal [V,2]')
+    B, step = H * W, int(batch_size)
+    if step < 1:
+        raise ValueError('render_views: batch_size = %d' % step)
+    if t_rand is not None and tuple(t_rand.shape) != (V, B, 1):
+        raise ValueError('render_views: t_rand is %s, expected [%d, %d, 1]' % (tuple(t_rand.shape), V, B))
+    Ro_t = torch.as_tensor(Ro, dtype=torch.float32, device=device).T.contiguous()
+    To = torch.as_tensor(To, dtype=torch.float32, device=device)
+    out = torch.empty(V, H, W, 3, dtype=torch.uint8, device=device)
+    with torch.no_grad():
+        for v in range(V):
+            rays_o, rays_d = image_rays({k: a[v:v + 1] for k, a in cams.items()}, H, W, device)
+            flat = out[v].view(B, 3)
+            for s in range(0, B, step):
+                kw = {} if t_rand is None else {'t_rand': t_rand[v, s:s + step]}
+                color = renderer.render(rays_o[s:s + step], rays_d[s:s + step], near, far, bt_inv, T_pose_21, None, Ro_t, To, **kw)['color_fine']
+                flat[s:s + step] = (color.detach().float().reshape(-1, 3) * 255.0).clamp(0, 255).to(torch.uint8)
+    return out
+
+
+# ---- image files: binary PPM by our own code (always there), anything else through PIL when it imports ---------------------------
+def write_image(path, img):
+    """uint8 [H, W, 3] (array or tensor) -> a file.  `.ppm`: binary PPM (P6, maxval 255), the channels stored as they are in the array.
+    Any other extension is handed to PIL; without PIL that is a RuntimeError."""
+    a = _host(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+        raise ValueError('write_image: expected a non-empty uint8 [H, W, 3] image, got %s %s' % (a.dtype, a.shape))
+    a = np.ascontiguousarray(a)
+    if os.path.splitext(str(path))[1].lower() == '.ppm':
+        with open(path, 'wb') as f:
+            f.write(b'P6\n%d %d\n255\n' % (a.shape[1], a.shape[0]))
+            f.write(a.tobytes())
+        return
+    _pil(path).fromarray(a).save(path)
+
+
+def read_image(path):
+    """A file -> uint8 [H, W, 3] numpy.  `.ppm`: the binary PPM `write_image` writes (P6, maxval 255; comments in the header are
+    allowed); any other extension through PIL (converted to RGB)."""
+    if os.path.splitext(str(path))[1].lower() != '.ppm':
+        with _pil(path).open(path) as im:
+            return np.ascontiguousarray(np.asarray(im.convert('RGB'), dtype=np.uint8))
+    with open(path, 'rb') as f:
+        data = f.read()
+    if data[:2] != b'P6':
+        raise ValueError('%s: not a binary PPM (magic %r)' % (path, data[:2]))
+    pos, fields = 2, []
+    while len(fields) < 3:                                      # width, height, maxval: decimal, separated by whitespace / comments
+        while pos < len(data) and (data[pos:pos + 1].isspace() or data[pos:pos + 1] == b'#'):
+            if data[pos:pos + 1] == b'#':
+                while pos < len(data) and data[pos:pos + 1] not in (b'\n', b'\r'):
+                    pos += 1
+            else:
+                pos += 1
+        end = pos
+        while end < len(data) and data[end:end + 1].isdigit():
+            end += 1
+        if end == pos:
+            raise ValueError('%s: truncated or malformed PPM header' % path)
+        fields.append(int(data[pos:end]))
+        pos = end
+    if not data[pos:pos + 1].isspace():
+        raise ValueError('%s: truncated or malformed PPM header' % path)
+    pos += 1                                                    # the single whitespace byte before the raster
+    w, h, maxval = fields
+    if maxval != 255:
+        raise ValueError('%s: maxval %d, only 8-bit PPM (maxval 255) is read' % (path, maxval))
+    if w < 1 or h < 1:
+        raise ValueError('%s: a %d x %d image' % (path, w, h))
+    if len(data) - pos < 3 * w * h:
+        raise ValueError('%s: truncated: %d bytes of pixels, %d x %d x 3 = %d expected' % (path, len(data) - pos, w, h, 3 * w * h))
+    return np.frombuffer(data, dtype=np.uint8, count=3 * w * h, offset=pos).reshape(h, w, 3).copy()
+
+
+def _pil(path):
+    try:
+        from PIL import Image
+    except ImportError:
+        raise RuntimeError('%s: only .ppm is read and written without PIL, and the module PIL does not import' % path)
+    return Image
 
 
 # ---- mesh export: the `mesh_*/{cid}_hand.ply` / `_obj.ply` files of get_res.py, without a mesh library --------------------------

@@ -176,6 +176,9 @@ SIGNATURES = {
     'hn_pm_paired': (c_i, [c_f, c_f, ctypes.c_longlong, ctypes.c_longlong, c_f, c_vp]),
     'hn_pm_row_mean': (c_i, [c_f, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp]),
     'hn_pm_accel': (c_i, [c_f, c_f, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp]),
+    'hn_im_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong]),
+    'hn_im_sse': (c_i, [c_vp, c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_sz, c_vp]),
+    'hn_im_ssim': (c_i, [c_vp, c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

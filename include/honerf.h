@@ -723,6 +723,25 @@ int hn_pm_paired(const float* a, const float* b, long long n_frames, long long n
 int hn_pm_row_mean(const float* x, long long n_rows, long long n_cols, double* mean, hn_stream_t stream);
 int hn_pm_accel(const float* gt, const float* pred, long long n_frames, long long n_points, double* accel, hn_stream_t stream);
 
+/* ---- image metrics (hn_imgmetric.hip): analys_results/analys_psnr_ssim_lpips.py:23-26 on the device -------------------------------
+ * Images are 8-bit interleaved RGB, [F, H, W, 3] uint8, F pairs of one size per call.  F >= 1, H and W >= 7, F x H x W x 3 below 2^31;
+ * a refused size, a NULL pointer (s_map excepted) or a workspace that is too small is HN_EINVAL with a message, before anything is
+ * launched, never a fault.  Nothing synchronises or allocates; every reduction runs in a fixed order without floating-point
+ * atomics: the same bits on every run.
+ *   hn_im_workspace_bytes: the workspace of one hn_im_sse or hn_im_ssim call (0 for sizes it refuses);
+ *   hn_im_sse: sse [F] = the exact sum over the image's H W 3 bytes of (a - b)^2 (compare_psnr, :23-24, is
+ *     10 log10(255^2 / (sse / (H W 3))); identical images give +inf);
+ *   hn_im_ssim: compare_ssim(a, b, channel_axis=2, data_range=255), :25-26: per channel a 7 x 7 uniform window, sample covariance
+ *     (49 / 48), C1 = (0.01 255)^2, C2 = (0.03 255)^2, S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)) from
+ *     exact integer window sums, evaluated in fp64, averaged over the (H - 6) x (W - 6) windows inside the image (skimage's crop
+ *     by 3 pixels) -> ssim_ch [F, 3] fp64, the per-channel means (the image's SSIM is the mean of the three); s_map, when not NULL,
+ *     receives S as fp32 [F, H - 6, W - 6, 3]. */
+size_t hn_im_workspace_bytes(long long n_images, long long height, long long width);
+int hn_im_sse(const unsigned char* a, const unsigned char* b, long long n_images, long long height, long long width, unsigned long long* sse,
+              void* workspace, size_t workspace_bytes, hn_stream_t stream);
+int hn_im_ssim(const unsigned char* a, const unsigned char* b, long long n_images, long long height, long long width, double* ssim_ch,
+               float* s_map, void* workspace, size_t workspace_bytes, hn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
