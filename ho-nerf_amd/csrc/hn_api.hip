@@ -273,6 +273,13 @@ void set_launch_n_pts_dev(const int* p) { g_launch_n_pts_dev = p; }
 static thread_local bool g_launch_dir_per_sample = false;
 bool launch_dir_per_sample() { return g_launch_dir_per_sample; }
 void set_launch_dir_per_sample(bool on) { g_launch_dir_per_sample = on; }
+static thread_local bool g_launch_three_pass = false;
+bool launch_three_pass() { return g_launch_three_pass; }
+struct ThreePassScope {   // around a taped render (hn_common.h: launch_three_pass)
+    const bool before;
+    explicit ThreePassScope(bool on) : before(g_launch_three_pass) { g_launch_three_pass = before || on; }
+    ~ThreePassScope() { g_launch_three_pass = before; }
+};
 static thread_local const int* g_launch_orig_idx = nullptr;
 const int* launch_orig_idx() { return g_launch_orig_idx; }
 void set_launch_orig_idx(const int* p) { g_launch_orig_idx = p; }
@@ -2050,6 +2057,7 @@ int hn_render_single_taped(const hn_field* f, const float* rays_o, const float* 
                            hn_stream_t stream) {
     HN_REQUIRE(f != nullptr, "null field");
     HN_REQUIRE(tape != nullptr, "hn_render_single_taped: tape is NULL");
+    ThreePassScope three_pass(true);
     return render_single_impl(f, rays_o, rays_d, t_rand, n_rays, near, far, n_samples, n_importance, up_sample_steps,
                               bt_inv, T_pose, color, cdf, weight_sum, weight_max, gradient_error, z_vals, workspace,
                               workspace_bytes, (hipStream_t)stream, nullptr, tape, tape_bytes);
@@ -2112,6 +2120,7 @@ int hn_render_dual(const hn_field* hand, const hn_field* obj, const float* rays_
                    float* grad_hand, float* grad_obj, float* gradient_error, float* z_vals, void* workspace,
                    size_t workspace_bytes, void* tape, size_t tape_bytes, int flags, hn_stream_t stream) {
     HN_REQUIRE(hand != nullptr && obj != nullptr, "null field");
+    ThreePassScope three_pass(tape != nullptr);
     return render_dual_impl(hand, obj, rays_o, rays_d, t_rand, n_frames, rays_per_frame, near, far, n_samples,
                             n_importance, up_sample_steps, bt_inv, T_pose, Ro, To, batch_quirk, color, weight_sum,
                             sdf_hand, sdf_obj, grad_hand, grad_obj, gradient_error, z_vals, workspace, workspace_bytes,

@@ -49,6 +49,9 @@ void set_launch_orig_idx(const int* p);
 const int* launch_frame_seg();
 void set_launch_frame_seg(const int* p);
 bool launch_dir_per_sample();     // hn_api.hip: the object adjoint launch writes d loss / d rays_d per sample (set around the launch)
+bool launch_three_pass();         // hn_api.hip: inside a render that keeps a TAPE (a backward pass follows) every launch of an HN_PREC_F16 field,
+                                  // the sdf-only ones of the importance rounds included, takes the fp32-equivalent kernels: the differentiable
+                                  // render of such a field is the HN_PREC_F16X3 field's, bit for bit
 int quad_max_blocks_override();   // hn_debug_quad_max_blocks: -1 = default selection of the latency-form kernels
 int pace_phantom_members();    // hn_debug_pace_phantom: members that never arrive at the XCD meetings (timeout-path test hook), 0 = off
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): `mask` is the kernel's own
@@ -176,6 +179,6 @@ struct hn_field {
     int sdf_out[9] = {}, sdf_in[9] = {}, col_out[5] = {}, col_in[5] = {};
     int sdf_ld[9] = {}, col_ld[5] = {};   // row pitch of the retained matrices (in_dim rounded up to a multiple of 4)
     int compact_far_field = 0;   // hn_field_set_compaction: the two-field renders evaluate only the samples with a live bone
-    int single_pass = 0;         // HN_PREC_F16: the evaluation kernels run their hidden layers on one f16 MFMA per product
+    int single_pass = 0;         // HN_PREC_F16 (either kind): the evaluation kernels run their hidden layers on one f16 MFMA per product
     int cull_far_field = 0;      // hn_field_set_culling: skip the chunks of bones whose mask is 0 for a whole workgroup
 };

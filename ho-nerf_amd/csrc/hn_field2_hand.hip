@@ -1372,7 +1372,8 @@ int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const flo
     }
     // a launch too small to fill the chip: the latency form (bit-identical results; its stash fits the same workspace)
     const int n_blocks = (n_pts + 31) / 32;
-    if (!full && !f->single_pass && n_blocks <= quad_max_blocks(n_cus) && field2_hand_q_workspace_bytes(n_blocks, n_cus) <= workspace_bytes)
+    const bool single_pass = f->single_pass && !launch_three_pass();   // HN_PREC_F16, outside a taped render
+    if (!full && !single_pass && n_blocks <= quad_max_blocks(n_cus) && field2_hand_q_workspace_bytes(n_blocks, n_cus) <= workspace_bytes)
         return launch_field2_hand_q(a, n_blocks, n_cus, stream);
     // XCD pacing: launches of many tiles per workgroup (the image-sized ones), where the workspace has the room
     if (HN_XCD_PACING && (n_pts + WG_SAMPLES - 1) / WG_SAMPLES >= XCD_PACE_MIN_ROUNDS * grid && workspace_bytes >= need + 64) {
@@ -1380,7 +1381,7 @@ int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const flo
         HN_CHECK_HIP(hipMemsetAsync(a.xsync, 0, 64, stream));
         if (const int ph = pace_phantom_members()) HN_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.xsync), ph, 8, stream));
     }
-    if (f->single_pass) return launch_field2_hand_f16(a, grid, full, stream);   // HN_PREC_F16
+    if (single_pass) return launch_field2_hand_f16(a, grid, full, stream);
     static std::atomic<uint64_t> lds_full{0}, lds_sdf{0};   // devices on which the LDS size attribute is set
     HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_hand<1>), (int)HAND2_LDS, &lds_full));
     HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_hand<0>), (int)HAND2_LDS, &lds_sdf));

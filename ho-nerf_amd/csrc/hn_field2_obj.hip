@@ -536,8 +536,43 @@ __device__ __forceinline__ void obj_adjoint(const Obj2Args& a, WStream& ws, Stas
 // form, per sample tile, with the tape in the wave's stash.  The fitting step splits mode 2 in two launches so that
 // nothing is evaluated twice: 3 = full evaluation that keeps its tape (stash slots per sample TILE, in a buffer the
 // caller keeps until the backward pass), 4 = the adjoint alone, from that tape.
-template <int MODE>
-__global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
+// HP: MFMA passes per product of the hidden layers -- 3: fp32-equivalent (HN_PREC_F16X3); 1: HN_PREC_F16, the single-pass
+// throughput mode (evaluation modes 0 / 1 only).  One pass: lin1, lin2, lin3, the hidden (193) columns of lin4, lin5, lin6 and
+// their W^T steps of the reverse sweep (722 k of the field's 1 342 k MACs per sample).  Which of the other layer groups drop to
+// one pass: the HN_F16_OBJ_* macros below.
+#ifndef HN_F16_OBJ_REV_PASSES
+#define HN_F16_OBJ_REV_PASSES 1   // W1^T .. W6^T of the reverse sweep (3: only the forward layers are single-pass)
+#endif
+#ifndef HN_F16_OBJ_X_PASSES
+#define HN_F16_OBJ_X_PASSES 3     // lin0 and lin4's skip columns: the 63 encoded inputs (sin / cos up to 2^9 x)
+#endif
+#ifndef HN_F16_OBJ_JAC_PASSES
+#define HN_F16_OBJ_JAC_PASSES 3   // W0^T dz0 + W4x^T dz4 in front of the encoding Jacobian (entries are multiplied by up to 2^9)
+#endif
+#ifndef HN_F16_OBJ_LIN78_PASSES
+#define HN_F16_OBJ_LIN78_PASSES 3 // lin7 (-> a8 -> sdf, the seed of the reverse sweep), lin8 (the feature vector) and W7^T
+#endif
+#ifndef HN_F16_OBJ_COLOR0_PASSES
+#define HN_F16_OBJ_COLOR0_PASSES 3  // colour lin0: reads the encodings of p, d and of the gradient
+#endif
+#ifndef HN_F16_OBJ_COLOR_PASSES
+#define HN_F16_OBJ_COLOR_PASSES 3   // colour lin1 .. lin3 (hidden 256 x 256, ReLU)
+#endif
+template <int MODE, int HP>
+__device__ __forceinline__ void field2_obj_body(const Obj2Args& a) {
+    static_assert(HP == 3 || MODE <= 1, "the single-pass mode exists for the evaluation kernels");
+    constexpr int PH = HP;                                      // lin1 .. lin6 (lin4: its hidden columns)
+    constexpr int PR = HP == 1 ? HN_F16_OBJ_REV_PASSES : 3;
+    constexpr int PX = HP == 1 ? HN_F16_OBJ_X_PASSES : 3;
+    constexpr int PJ = HP == 1 ? HN_F16_OBJ_JAC_PASSES : 3;
+    constexpr int P78 = HP == 1 ? HN_F16_OBJ_LIN78_PASSES : 3;
+    constexpr int PC0 = HP == 1 ? HN_F16_OBJ_COLOR0_PASSES : 3;
+    constexpr int PC = HP == 1 ? HN_F16_OBJ_COLOR_PASSES : 3;
+    using LoH = std::bool_constant<PH == 3>;     // what a layer's output fragments need: lo halves only for a three-pass consumer
+    using LoR = std::bool_constant<PR == 3>;
+    using LoJ = std::bool_constant<PJ == 3>;
+    using Lo78 = std::bool_constant<P78 == 3>;
+    constexpr int L4X = PX == 3 ? 12 : 16;                      // lin4: k-steps 12 .. 15 are the encoded inputs (and a4[192] in their pad slot)
     constexpr bool FULL = MODE >= 1;
     constexpr bool ADJ = MODE >= 2;                    // the forward pass writes the tape
     constexpr bool RUN_FWD = MODE != 4 && MODE != 5;
@@ -622,10 +657,13 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
             };
         };
         // ... and, in the full kernel, the fp32 activation to the stash for the reverse sweep
-        auto to_regs_keep = [&](h8(&oh)[16], h8(&ol)[16], int stash_slot) {
+        // (LO_: the layer that reads these fragments takes three passes.  A single-pass consumer reads the hi fragments only: the lo
+        //  halves are then neither formed -- the epilogue's last phase goes away -- nor kept in registers)
+        auto to_regs_keep = [&](auto LO_, h8(&oh)[16], h8(&ol)[16], int stash_slot) {
             return [&oh, &ol, stash_slot, &sh, &a](auto T, EpiState& st, const auto&) {
                 constexpr int t = decltype(T)::value;
                 (void)a;
+                if constexpr (decltype(LO_)::value) {
                 asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
                 oh[2 * t] = st.hi[0];
                 ol[2 * t] = st.lo[0];
@@ -634,6 +672,15 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
 #if HN_PARK_AGPR
                 asm volatile("" : "+a"(oh[2 * t]), "+a"(ol[2 * t]), "+a"(oh[2 * t + 1]), "+a"(ol[2 * t + 1]));   // as hn_field2_hand.hip: park
 #endif
+                } else {
+                    (void)ol;
+                    asm volatile("" : "+v"(st.hi[0]), "+v"(st.hi[1]));
+                    oh[2 * t] = st.hi[0];
+                    oh[2 * t + 1] = st.hi[1];
+#if HN_PARK_AGPR
+                    asm volatile("" : "+a"(oh[2 * t]), "+a"(oh[2 * t + 1]));
+#endif
+                }
                 if (FULL && !(HN_DBG(a) & 1)) sh.tile_store(stash_slot, t, st.vec());
                 return NoData{};
             };
@@ -654,16 +701,19 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
                 x16h[s] = xh[s];
                 x16l[s] = xl[s];
             }
-            run_layer_c<8, 4, 4, true, true, CB_L0, CB_HID>(ws, x16h, x16l, lane, h, no_pre, PhSoftplus{}, to_regs_keep(ah, al, OS_A1 + 0), no_store);
+            run_layer_c<8, 4, 4, true, true, CB_L0, CB_HID, PX>(ws, x16h, x16l, lane, h, no_pre, PhSoftplus{}, to_regs_keep(LoH{}, ah, al, OS_A1 + 0), no_store);
         }
-        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_keep(bh, bl, OS_A1 + 1), no_store);   // lin1
-        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID>(ws, bh, bl, lane, h, no_pre, PhSoftplus{}, to_regs_keep(ah, al, OS_A1 + 2), no_store);   // lin2
+        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_keep(LoH{}, bh, bl, OS_A1 + 1), no_store);   // lin1
+        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSoftplus{}, to_regs_keep(LoH{}, ah, al, OS_A1 + 2), no_store);   // lin2
         // ---- lin3: 193 outputs = 7 tiles (tile 6 holds neuron 192 in row 0)
         float a4_192 = 0.f;
-        run_layer_c<7, 16, 1, true, true, CB_HID, CB_HID>(ws, ah, al, lane, h, no_pre, PhSoftplus{},
+        run_layer_c<7, 16, 1, true, true, CB_HID, CB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSoftplus{},
                                         [&](auto T, EpiState& st, const auto&) {
                                             constexpr int t = decltype(T)::value;
-                                            asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
+                                            if constexpr (LoH::value)
+                                                asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
+                                            else
+                                                asm volatile("" : "+v"(st.hi[0]), "+v"(st.hi[1]));
                                             if constexpr (t == 6) {
                                                 // rows 193..223 are padding (zero weights and bias give softplus(0)): drop them
 #pragma unroll
@@ -671,9 +721,11 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
                                                 a4_192 = st.v[0];
                                             } else {
                                                 bh[2 * t] = st.hi[0];
-                                                bl[2 * t] = st.lo[0];
                                                 bh[2 * t + 1] = st.hi[1];
-                                                bl[2 * t + 1] = st.lo[1];
+                                                if constexpr (LoH::value) {   // (lin4's hidden columns at one pass read no lo fragments)
+                                                    bl[2 * t] = st.lo[0];
+                                                    bl[2 * t + 1] = st.lo[1];
+                                                }
                                             }
                                             if (FULL && !(HN_DBG(a) & 1)) sh.tile_store(OS_A1 + 3, t, st.vec());
                                             return NoData{};
@@ -697,13 +749,13 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
             bh[15][7] = h ? vh : bh[15][7];
             bl[15][7] = h ? vl : bl[15][7];
         }
-        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID>(ws, bh, bl, lane, h, no_pre, PhSoftplus{}, to_regs_keep(ah, al, OS_A1 + 4), no_store);   // lin4
-        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_keep(bh, bl, OS_A1 + 5), no_store);   // lin5
-        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID>(ws, bh, bl, lane, h, no_pre, PhSoftplus{}, to_regs_keep(ah, al, OS_A1 + 6), no_store);   // lin6
+        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID, PH, L4X>(ws, bh, bl, lane, h, no_pre, PhSoftplus{}, to_regs_keep(LoH{}, ah, al, OS_A1 + 4), no_store);   // lin4
+        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_keep(LoH{}, bh, bl, OS_A1 + 5), no_store);   // lin5
+        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSoftplus{}, to_regs_keep(Lo78{}, ah, al, OS_A1 + 6), no_store);   // lin6
         // ---- lin7 -> a8; sdf = W8[0,:] a8 + b8; seed of the reverse sweep dz7 = sigma'(z7) W8[0,:] / scale
         float sdf_acc = 0.f;
         auto lin7 = [&](auto NA_) {   // NA_: the size of the chunk that follows the layer, a constant
-        run_layer_c<8, 16, 1, true, true, CB_HID, decltype(NA_)::value>(
+        run_layer_c<8, 16, 1, true, true, CB_HID, decltype(NA_)::value, P78>(
             ws, ah, al, lane, h,
             [&](auto, const char* tail) { return Act{tail_tile(tail, 1, h)}; }, PhSoftplus{},
             [&](auto T, EpiState& st, const Act& w8) {
@@ -751,7 +803,7 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
         }
 
         // ---- lin8 rows 1..256: the feature vector (no activation) -> stash as fragments for colour lin0
-        run_layer_c<8, 16, 1, true, true, CB_HID, CB_BWD>(
+        run_layer_c<8, 16, 1, true, true, CB_HID, CB_BWD, P78>(
             ws, bh, bl, lane, h, no_pre, PhIdentity{},
             [&](auto T, EpiState& st, const auto&) {
                 constexpr int t = decltype(T)::value;
@@ -775,9 +827,10 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) sh.frag_load(OS_DZ7 * SLOT_BYTES, s, ah[s], al[s]);
         // (adjoint mode: every dz_l also goes to the stash as an fp32 tile, slot OS_DZ + l)
-        auto to_regs_dz = [&](h8(&oh)[16], h8(&ol)[16], int dz_slot) {
+        auto to_regs_dz = [&](auto LO_, h8(&oh)[16], h8(&ol)[16], int dz_slot) {
             return [&oh, &ol, dz_slot, &sh](auto T, EpiState& st, const auto&) {
                 constexpr int t = decltype(T)::value;
+                if constexpr (decltype(LO_)::value) {
                 asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
                 oh[2 * t] = st.hi[0];
                 ol[2 * t] = st.lo[0];
@@ -786,13 +839,22 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
 #if HN_PARK_AGPR
                 asm volatile("" : "+a"(oh[2 * t]), "+a"(ol[2 * t]), "+a"(oh[2 * t + 1]), "+a"(ol[2 * t + 1]));
 #endif
+                } else {
+                    (void)ol;
+                    asm volatile("" : "+v"(st.hi[0]), "+v"(st.hi[1]));
+                    oh[2 * t] = st.hi[0];
+                    oh[2 * t + 1] = st.hi[1];
+#if HN_PARK_AGPR
+                    asm volatile("" : "+a"(oh[2 * t]), "+a"(oh[2 * t + 1]));
+#endif
+                }
                 if constexpr (ADJ) sh.tile_store(dz_slot, t, st.vec());
                 return NoData{};
             };
         };
-        run_layer_c<8, 16, 1, false, true, CB_BWD, CB_BWD>(ws, ah, al, lane, h, act_of(OS_A1 + 6), PhDsig{}, to_regs_dz(bh, bl, OS_DZ + 6), no_store);   // W7^T -> dz6
-        run_layer_c<8, 16, 1, false, true, CB_BWD, CB_BWD>(ws, bh, bl, lane, h, act_of(OS_A1 + 5), PhDsig{}, to_regs_dz(ah, al, OS_DZ + 5), no_store);   // W6^T -> dz5
-        run_layer_c<8, 16, 1, false, true, CB_BWD, CB_BWD>(ws, ah, al, lane, h, act_of(OS_A1 + 4), PhDsig{},                          // W5^T -> dz4 (kept)
+        run_layer_c<8, 16, 1, false, true, CB_BWD, CB_BWD, P78>(ws, ah, al, lane, h, act_of(OS_A1 + 6), PhDsig{}, to_regs_dz(LoR{}, bh, bl, OS_DZ + 6), no_store);   // W7^T -> dz6
+        run_layer_c<8, 16, 1, false, true, CB_BWD, CB_BWD, PR>(ws, bh, bl, lane, h, act_of(OS_A1 + 5), PhDsig{}, to_regs_dz(LoR{}, ah, al, OS_DZ + 5), no_store);   // W6^T -> dz5
+        run_layer_c<8, 16, 1, false, true, CB_BWD, CB_BWD, PR>(ws, ah, al, lane, h, act_of(OS_A1 + 4), PhDsig{},                          // W5^T -> dz4 (kept)
                                          [&](auto T, EpiState& st, const auto&) {
                                              constexpr int t = decltype(T)::value;
                                              asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
@@ -806,33 +868,38 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
                                          },
                                          no_store);
         // W4[:, :193]^T: dz4 -> dz3 (193 rows = 7 tiles; a4's padding rows were stashed as 0 => sigma' = 0)
-        run_layer_c<7, 16, 1, false, true, CB_BWD, CB_BWD3>(ws, bh, bl, lane, h, act_of(OS_A1 + 3), PhDsig{},
+        run_layer_c<7, 16, 1, false, true, CB_BWD, CB_BWD3, PR>(ws, bh, bl, lane, h, act_of(OS_A1 + 3), PhDsig{},
                                          [&](auto T, EpiState& st, const auto&) {
                                              constexpr int t = decltype(T)::value;
-                                             asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
+                                             if constexpr (LoR::value)
+                                                 asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
+                                             else
+                                                 asm volatile("" : "+v"(st.hi[0]), "+v"(st.hi[1]));
                                              if constexpr (t < 6) {
                                                  ah[2 * t] = st.hi[0];
-                                                 al[2 * t] = st.lo[0];
                                                  ah[2 * t + 1] = st.hi[1];
-                                                 al[2 * t + 1] = st.lo[1];
+                                                 if constexpr (LoR::value) {
+                                                     al[2 * t] = st.lo[0];
+                                                     al[2 * t + 1] = st.lo[1];
+                                                 }
                                              } else {
                                                  ah[12] = st.hi[0];   // only k-step 12 exists (neuron 192); 13 is padding
-                                                 al[12] = st.lo[0];
+                                                 if constexpr (LoR::value) al[12] = st.lo[0];
                                              }
                                              if constexpr (ADJ) sh.tile_store(OS_DZ + 3, t, st.vec());
                                              return NoData{};
                                          },
                                          no_store);
-        run_layer_c<8, 13, 1, false, true, CB_BWD3, CB_BWD>(ws, ah, al, lane, h, act_of(OS_A1 + 2), PhDsig{}, to_regs_dz(bh, bl, OS_DZ + 2), no_store);   // W3^T -> dz2
-        run_layer_c<8, 16, 1, false, true, CB_BWD, CB_BWD>(ws, bh, bl, lane, h, act_of(OS_A1 + 1), PhDsig{}, to_regs_dz(ah, al, OS_DZ + 1), no_store);    // W2^T -> dz1
-        run_layer_c<8, 16, 1, false, true, CB_BWD, CB_BWD>(ws, ah, al, lane, h, act_of(OS_A1 + 0), PhDsig{}, to_regs_dz(bh, bl, OS_DZ + 0), no_store);    // W1^T -> dz0
+        run_layer_c<8, 13, 1, false, true, CB_BWD3, CB_BWD, PR>(ws, ah, al, lane, h, act_of(OS_A1 + 2), PhDsig{}, to_regs_dz(LoR{}, bh, bl, OS_DZ + 2), no_store);   // W3^T -> dz2
+        run_layer_c<8, 16, 1, false, true, CB_BWD, CB_BWD, PR>(ws, bh, bl, lane, h, act_of(OS_A1 + 1), PhDsig{}, to_regs_dz(LoR{}, ah, al, OS_DZ + 1), no_store);    // W2^T -> dz1
+        run_layer_c<8, 16, 1, false, true, CB_BWD, CB_BWD, PR>(ws, ah, al, lane, h, act_of(OS_A1 + 0), PhDsig{}, to_regs_dz(LoJ{}, bh, bl, OS_DZ + 0), no_store);    // W1^T -> dz0
         // d sdf / d X-space = W0^T dz0 + W4[:, 193:]^T dz4   (64 rows = 2 tiles; row <-> k-slot of the same lane)
         f32x16 G1[2] = {zero16(), zero16()}, G2[2] = {zero16(), zero16()};
         static_for<2>([&](auto U) {
             constexpr int u = decltype(U)::value;
             const char* buf = ws.template acquire<0>();
             ws.template begin_c<CB_BWD>();
-            mma_tile<16, 0, CB_BWD>(ws, buf, bh, bl, G1[u], G2[u], lane);
+            mma_tile<16, 0, CB_BWD, PJ>(ws, buf, bh, bl, G1[u], G2[u], lane);
         });
 #pragma unroll
         for (int s = 0; s < 16; ++s) sh.frag_load(OS_DZ4 * SLOT_BYTES, s, ah[s], al[s]);
@@ -841,7 +908,7 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
             const char* buf = ws.template acquire<0>();
             constexpr int nbytes = u == 0 ? CB_BWD : CB_C0A;
             ws.template begin_c<nbytes>();
-            mma_tile<16, 0, nbytes>(ws, buf, ah, al, G1[u], G2[u], lane);
+            mma_tile<16, 0, nbytes, PJ>(ws, buf, ah, al, G1[u], G2[u], lane);
         });
         // ---- Jacobian of the encoding (in-lane: G row of tile u, register 8(s&1)+j <-> k-slot (s = 2u + .., h, j))
         {
@@ -925,17 +992,17 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
                 c2[t & 1] = zero16();
                 if constexpr (t > 0) {
                     Epi<true, PhRelu, NoData> epi{st, relu, nd};
-                    mma_tile<16, 0, CB_C0B>(ws, bufa, ah, al, c1[t & 1], c2[t & 1], lane, epi);
+                    mma_tile<16, 0, CB_C0B, PC0>(ws, bufa, ah, al, c1[t & 1], c2[t & 1], lane, epi);
                     split_finish<true>(st);
                     put(std::integral_constant<int, t - 1>{});
                 } else {
-                    mma_tile<16, 0, CB_C0B>(ws, bufa, ah, al, c1[t & 1], c2[t & 1], lane);
+                    mma_tile<16, 0, CB_C0B, PC0>(ws, bufa, ah, al, c1[t & 1], c2[t & 1], lane);
                 }
                 const char* bufb = ws.template acquire<0>();
                 constexpr int nbytes = t + 1 < 8 ? CB_C0A : CB_HID;
                 ws.template begin_c<nbytes>();
                 const f32x16 bias = tail_tile(bufb + 8 * KS_BYTES, 0, h);
-                mma_tile<8, 0, nbytes>(ws, bufb, mh, ml, c1[t & 1], c2[t & 1], lane);
+                mma_tile<8, 0, nbytes, PC0>(ws, bufb, mh, ml, c1[t & 1], c2[t & 1], lane);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) c1[t & 1][i] += bias[i];
             });
@@ -963,13 +1030,13 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
                 return NoData{};
             };
         };
-        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID>(ws, bh, bl, lane, h, no_pre, PhRelu{}, to_regs_c(ah, al, OS_C + 1), no_store);   // colour lin1
-        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID>(ws, ah, al, lane, h, no_pre, PhRelu{}, to_regs_c(bh, bl, OS_C + 2), no_store);   // colour lin2
+        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID, PC>(ws, bh, bl, lane, h, no_pre, PhRelu{}, to_regs_c(ah, al, OS_C + 1), no_store);   // colour lin1
+        run_layer_c<8, 16, 1, true, true, CB_HID, CB_HID, PC>(ws, ah, al, lane, h, no_pre, PhRelu{}, to_regs_c(bh, bl, OS_C + 2), no_store);   // colour lin2
         struct W3 {
             f32x16 w[3];
         };
         auto col3 = [&](auto NA_) {
-        run_layer_c<8, 16, 1, true, false, CB_HID, decltype(NA_)::value>(   // colour lin3 + the 3 rows of lin4 (tail slots 1..3)
+        run_layer_c<8, 16, 1, true, false, CB_HID, decltype(NA_)::value, PC>(   // colour lin3 + the 3 rows of lin4 (tail slots 1..3)
             ws, bh, bl, lane, h,
             [&](auto, const char* tail) { return W3{{tail_tile(tail, 1, h), tail_tile(tail, 2, h), tail_tile(tail, 3, h)}}; },
             PhRelu{},
@@ -1011,8 +1078,36 @@ __global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
     }
 }
 
-#ifndef HN_OBJ_QUAD_TU   // hn_field2_obj_q.hip includes this file for its device helpers only
+
+// the kernels proper: k_field2_obj<MODE> (fp32-equivalent, the names the profiles of every round carry) and the single-pass
+// evaluation kernels of HN_PREC_F16
+template <int MODE>
+__global__ __launch_bounds__(256) void k_field2_obj(const Obj2Args a) {
+    field2_obj_body<MODE, 3>(a);
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void k_field2_obj_f16(const Obj2Args a) {
+    field2_obj_body<MODE, 1>(a);
+}
+
+#if defined(HN_OBJ_QUAD_TU)   // hn_field2_obj_q.hip includes this file for its device helpers only
+#elif defined(HN_OBJ_F16_TU)  // hn_field2_obj_f16.hip: the evaluation kernels of HN_PREC_F16 (single-pass hidden layers)
 constexpr size_t OBJ2_LDS = 2 * CHUNK_MAX;
+int launch_field2_obj_f16(const Obj2Args& a, int grid, bool full, hipStream_t stream) {
+    static std::atomic<uint64_t> lds_full{0}, lds_sdf{0};
+    HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_obj_f16<1>), (int)OBJ2_LDS, &lds_full));
+    HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_obj_f16<0>), (int)OBJ2_LDS, &lds_sdf));
+    if (full)
+        hipLaunchKernelGGL(k_field2_obj_f16<1>, dim3(grid), dim3(256), OBJ2_LDS, stream, a);
+    else
+        hipLaunchKernelGGL(k_field2_obj_f16<0>, dim3(grid), dim3(256), OBJ2_LDS, stream, a);
+    HN_LAUNCH_CHECK();
+    return HN_OK;
+}
+#else
+constexpr size_t OBJ2_LDS = 2 * CHUNK_MAX;
+
+int launch_field2_obj_f16(const Obj2Args& a, int grid, bool full, hipStream_t stream);   // hn_field2_obj_f16.hip
 
 int launch_field2_obj_q(const Obj2Args& a, int n_blocks, int n_cus, hipStream_t stream);   // hn_field2_obj_q.hip
 // Grid of the TAPED evaluation and of the adjoint from a tape (modes 3 / 4: their stash is indexed by tile, so any grid works).  These
@@ -1104,12 +1199,15 @@ int launch_field2_obj(const hn_field* f, const float* pts, const float* rays_d, 
         if (const int ph = pace_phantom_members()) HN_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a.xsync), ph, 8, stream));
         }
     }
-    // an sdf-only launch too small to fill the chip: the latency form (hn_field2_obj_q.hip; bit-identical results)
-    {
+    // an sdf-only launch too small to fill the chip: the latency form (hn_field2_obj_q.hip; bit-identical results).  Not for a
+    // single-pass field: sdf() and the sdf of a full evaluation take the same passes
+    const bool single_pass = f->single_pass && !launch_three_pass();   // HN_PREC_F16, outside a taped render
+    if (!single_pass) {
         const int n_blocks = (n_pts + 31) / 32;
         const int qmax = quad_max_blocks_override();
         if (!full && n_blocks <= (qmax >= 0 ? qmax : 2 * n_cus)) return launch_field2_obj_q(a, n_blocks, n_cus, stream);
     }
+    if (single_pass) return launch_field2_obj_f16(a, grid, full, stream);
     static std::atomic<uint64_t> lds_full{0}, lds_sdf{0};   // devices on which the LDS size attribute is set
     HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_obj<1>), (int)OBJ2_LDS, &lds_full));
     HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_obj<0>), (int)OBJ2_LDS, &lds_sdf));
@@ -1193,11 +1291,11 @@ int launch_field2_obj_adj(const hn_field* f, const float* pts, const float* rays
     return HN_OK;
 }
 
-#endif   // HN_OBJ_QUAD_TU
+#endif   // HN_OBJ_QUAD_TU / HN_OBJ_F16_TU
 }  // namespace v2
 }  // namespace hn
 
-#if defined(HN_TS) && !defined(HN_OBJ_QUAD_TU)
+#if defined(HN_TS) && !defined(HN_OBJ_QUAD_TU) && !defined(HN_OBJ_F16_TU)
 // timing builds (tools/ts_report_obj.py): workgroup 0's per-chunk stamps of the last object-field launch
 extern "C" int hn_debug_ts_obj(unsigned long long* host, int n) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(hn::v2::g_hn_ts), sizeof(unsigned long long) * n);

@@ -549,7 +549,9 @@ struct NoEpi {
 #endif
 // FETCH: 0 none; 1 the run-time form (WStream::begin / piece); >= 1024: the size of the chunk being fetched, a
 // constant (WStream::begin_c / piece_c)
-template <int KS, int S0, int FETCH, int PASSES = 3, int NX, typename Epi>
+// S3 (with PASSES == 1): k-steps S3 .. KS-1 of the tile take three passes all the same (the object field's lin4: its hidden columns
+// are followed by the columns over the encoded inputs, in one tile)
+template <int KS, int S0, int FETCH, int PASSES = 3, int S3 = KS, int NX, typename Epi>
 __device__ __forceinline__ void mma_tile(WStream& ws, const char* blk, const h8 (&xh)[NX], const h8 (&xl)[NX], f32x16& c1,
                                          f32x16& c2, int lane, Epi& epi) {
     static_assert(S0 + KS <= NX, "k-step range");
@@ -566,7 +568,7 @@ __device__ __forceinline__ void mma_tile(WStream& ws, const char* blk, const h8 
     auto load = [&](auto S) {
         constexpr int s = decltype(S)::value;
         ah[s % 3] = *reinterpret_cast<const h8*>(lblk + s * KS_BYTES);
-        if constexpr (PASSES == 3) al[s % 3] = *reinterpret_cast<const h8*>(lblk + s * KS_BYTES + 1024);
+        if constexpr (PASSES == 3 || s >= S3) al[s % 3] = *reinterpret_cast<const h8*>(lblk + s * KS_BYTES + 1024);
     };
     auto slot = [&](auto Q_) {
         constexpr int Q = decltype(Q_)::value;
@@ -581,15 +583,15 @@ __device__ __forceinline__ void mma_tile(WStream& ws, const char* blk, const h8 
     static_for<KS>([&](auto S) {
         constexpr int s = decltype(S)::value;
         if constexpr (s + 2 < KS) load(std::integral_constant<int, s + 2>{});
-        mma_block<s, S0, PASSES>(ah[s % 3], al[s % 3], xh, xl, c1, c2, slot);
+        mma_block<s, S0, (s >= S3 ? 3 : PASSES)>(ah[s % 3], al[s % 3], xh, xl, c1, c2, slot);
     });
     ws.stamp(4);
 }
-template <int KS, int S0, int FETCH, int PASSES = 3, int NX>
+template <int KS, int S0, int FETCH, int PASSES = 3, int S3 = KS, int NX>
 __device__ __forceinline__ void mma_tile(WStream& ws, const char* blk, const h8 (&xh)[NX], const h8 (&xl)[NX], f32x16& c1,
                                          f32x16& c2, int lane) {
     NoEpi e;
-    mma_tile<KS, S0, FETCH, PASSES>(ws, blk, xh, xl, c1, c2, lane, e);
+    mma_tile<KS, S0, FETCH, PASSES, S3>(ws, blk, xh, xl, c1, c2, lane, e);
 }
 
 // A whole chunk of NT tiles x KS k-steps that share the KS fragments xh/xl (the hand field's feature passes):
@@ -913,7 +915,7 @@ __device__ __forceinline__ void arm(EpiState& st) {
 // next_same / next_after: bytes of the chunk that follows a chunk of this layer (another of the same
 // layer / the first of the next layer; 0 = none).
 // NS / NA >= 0: next_same / next_after as constants (the compile-time-sized fetch of WStream); -1: the run-time arguments.
-template <int OT, int KS, int TPC, bool TAIL, bool FRAGS, int NS, int NA, int PASSES, int NX, typename Pre, typename Ph, typename Fin, typename Store>
+template <int OT, int KS, int TPC, bool TAIL, bool FRAGS, int NS, int NA, int PASSES, int S3, int NX, typename Pre, typename Ph, typename Fin, typename Store>
 __device__ __forceinline__ void run_layer_impl(WStream& ws, int next_same, int next_after, const h8 (&xh)[NX], const h8 (&xl)[NX],
                                                int lane, int h, Pre&& pre, Ph&& ph, Fin&& fin, Store&& store) {
     static_assert((NS >= 0) == (NA >= 0), "both sizes constant or both run-time");
@@ -945,11 +947,11 @@ __device__ __forceinline__ void run_layer_impl(WStream& ws, int next_same, int n
         pd[t & 1] = pre(T, tail);
         if constexpr (t > 0) {
             Epi<FRAGS, std::remove_reference_t<Ph>, PD> epi{st, ph, pd[(t - 1) & 1]};
-            mma_tile<KS, 0, fetch, PASSES>(ws, buf + (t % TPC) * KS * KS_BYTES, xh, xl, c1[t & 1], c2[t & 1], lane, epi);
+            mma_tile<KS, 0, fetch, PASSES, S3>(ws, buf + (t % TPC) * KS * KS_BYTES, xh, xl, c1[t & 1], c2[t & 1], lane, epi);
             split_finish<FRAGS>(st);
             held = fin(std::integral_constant<int, t - 1>{}, st, pd[(t - 1) & 1]);
         } else {
-            mma_tile<KS, 0, fetch, PASSES>(ws, buf + (t % TPC) * KS * KS_BYTES, xh, xl, c1[t & 1], c2[t & 1], lane);
+            mma_tile<KS, 0, fetch, PASSES, S3>(ws, buf + (t % TPC) * KS * KS_BYTES, xh, xl, c1[t & 1], c2[t & 1], lane);
         }
     });
     if constexpr (OT >= 2) store(std::integral_constant<int, OT - 2>{}, held);
@@ -965,12 +967,12 @@ __device__ __forceinline__ void run_layer_impl(WStream& ws, int next_same, int n
 template <int OT, int KS, int TPC, bool TAIL, bool FRAGS, int NX, typename Pre, typename Ph, typename Fin, typename Store>
 __device__ __forceinline__ void run_layer(WStream& ws, int next_same, int next_after, const h8 (&xh)[NX], const h8 (&xl)[NX],
                                           int lane, int h, Pre&& pre, Ph&& ph, Fin&& fin, Store&& store) {
-    run_layer_impl<OT, KS, TPC, TAIL, FRAGS, -1, -1, 3>(ws, next_same, next_after, xh, xl, lane, h, pre, ph, fin, store);
+    run_layer_impl<OT, KS, TPC, TAIL, FRAGS, -1, -1, 3, KS>(ws, next_same, next_after, xh, xl, lane, h, pre, ph, fin, store);
 }
-template <int OT, int KS, int TPC, bool TAIL, bool FRAGS, int NS, int NA, int PASSES = 3, int NX, typename Pre, typename Ph, typename Fin, typename Store>
+template <int OT, int KS, int TPC, bool TAIL, bool FRAGS, int NS, int NA, int PASSES = 3, int S3 = KS, int NX, typename Pre, typename Ph, typename Fin, typename Store>
 __device__ __forceinline__ void run_layer_c(WStream& ws, const h8 (&xh)[NX], const h8 (&xl)[NX], int lane, int h, Pre&& pre,
                                             Ph&& ph, Fin&& fin, Store&& store) {
-    run_layer_impl<OT, KS, TPC, TAIL, FRAGS, NS, NA, PASSES>(ws, 0, 0, xh, xl, lane, h, pre, ph, fin, store);
+    run_layer_impl<OT, KS, TPC, TAIL, FRAGS, NS, NA, PASSES, S3>(ws, 0, 0, xh, xl, lane, h, pre, ph, fin, store);
 }
 
 // standard phases ---------------------------------------------------------------------------------

@@ -66,7 +66,11 @@ def render_views(renderer, cameras, H, W, near, far, bt_inv, T_pose_21, Ro, To, 
     Per camera the full NDC grid goes through `image_rays` and then through `renderer.render(.., None, Ro.T, To)` in chunks of
     `batch_size` rays under torch.no_grad() (:263-281; the chunks keep the per-sample outputs of a full image, about 1 GB at
     512 x 334 x 192 samples, out of memory).  `color_fine` is quantised on the device exactly as `to_image` does on the host: fp32
-    * 255, clamp to [0, 255], truncate.  `t_rand` is [V, H*W, 1] (the stratified jitter, fixed for a reproducible render) or None."""
+    * 255, clamp to [0, 255], truncate.  `t_rand` is [V, H*W, 1] (the stratified jitter, fixed for a reproducible render) or None.
+
+    There is no argument for the arithmetic: the renderer's `precision` selects it.  These renders keep no tape, so `'f16'` runs BOTH
+    fields' single-pass evaluation kernels (k_field2_hand_f16 / k_field2_obj_f16; DESIGN.md 3.17 has the speed and the PSNR / SSIM cost
+    against the default `'f16x3'` views)."""
     device = torch.device('cuda')
     cams = {k: np.asarray(cameras[k], dtype=np.float32) for k in ('R', 'T', 'focal', 'principal')}
     V = cams['R'].shape[0]

@@ -17,7 +17,7 @@ HN_FIELD_OBJ = 0
 HN_FIELD_HAND = 1
 HN_PREC_FP32 = 0
 HN_PREC_F16X3 = 1
-HN_PREC_F16 = 2           # single-pass throughput mode of the evaluation kernels (include/honerf.h)
+HN_PREC_F16 = 2           # single-pass throughput mode of the evaluation kernels, hand and obj fields (include/honerf.h)
 HN_DUAL_RO_TRANSPOSED, HN_DUAL_OBJ_POSE_ON_SIDE, HN_DUAL_BWD_NO_JOIN = 1, 2, 4      # flags of hn_render_dual / _bwd
 HN_PACK_EVAL_ONLY = 0x100     # no adjoint weight streams (fields re-packed every training step)
 PRECISIONS = {'fp32': HN_PREC_FP32, 'f16x3': HN_PREC_F16X3, 'f16': HN_PREC_F16}

@@ -46,7 +46,8 @@ extern "C" {
                           * renders without a tape) run the hidden layers of both networks on ONE f16 MFMA per product (fp16
                           * operands, fp32 accumulation); the encodings, the feature layers, the last SDF layer, the alpha
                           * stage and every adjoint / taped kernel stay fp32-equivalent.  Error ~1e-3 (tests pin it):
-                          * a secondary figure, never the parity path.  Hand fields; an obj field behaves as F16X3. */
+                          * a secondary figure, never the parity path.  Hand and obj fields (k_field2_hand_f16 /
+                          * k_field2_obj_f16: which layers take one pass is listed at their HN_F16_* macros). */
 /* OR-ed into `precision` at hn_field_create: pack the evaluation programs only, no adjoint weight streams.  For fields
  * that are re-packed every optimiser step (training, honerf_amd/training.py): their backward pass is
  * hn_field_param_bwd / hn_render_single_bwd, which work on the retained row-major matrices; hn_field_eval_bwd and
