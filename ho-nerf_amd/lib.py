@@ -179,6 +179,11 @@ SIGNATURES = {
     'hn_im_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong]),
     'hn_im_sse': (c_i, [c_vp, c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_sz, c_vp]),
     'hn_im_ssim': (c_i, [c_vp, c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'hn_lpips_create': (c_i, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    'hn_lpips_destroy': (c_i, [c_vp]),
+    'hn_lpips_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong]),
+    'hn_lpips': (c_i, [c_vp, c_vp, c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_sz, c_vp]),
+    'hn_lpips_features': (c_i, [c_vp, c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 
 _lib = None

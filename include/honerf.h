@@ -14,7 +14,7 @@
  *     int64, to match torch) unless a parameter is documented as host;
  *   - the last argument is the hipStream_t to launch on (as void*); no entry
  *     point synchronises, allocates or frees device memory except
- *     hn_field_create / hn_field_destroy / hn_workspace_* (and hn_render_single_bwd
+ *     hn_field_create / hn_field_destroy / hn_lpips_create / hn_lpips_destroy / hn_workspace_* (and hn_render_single_bwd
  *     on a hand field with hn_field_set_compaction, which reads one count back);
  *   - outputs and workspaces are caller-owned; sizes come from the
  *     *_workspace_bytes queries.
@@ -742,6 +742,34 @@ int hn_im_sse(const unsigned char* a, const unsigned char* b, long long n_images
               void* workspace, size_t workspace_bytes, hn_stream_t stream);
 int hn_im_ssim(const unsigned char* a, const unsigned char* b, long long n_images, long long height, long long width, double* ssim_ch,
                float* s_map, void* workspace, size_t workspace_bytes, hn_stream_t stream);
+
+/* ---- LPIPS (hn_lpips.hip): analys_results/analys_psnr_ssim_lpips.py:28-33,44 on the device -------------------------------------------
+ * lpips.LPIPS(net='vgg') in its defaults (version 0.1, linear layers on, spatial off, eval mode) on x = u8 / 128 - 1: the scaling
+ * layer, VGG16's 13 3x3 convolutions with ReLU (module indices 0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28; MaxPool2d(2, 2), floor
+ * mode, after 2, 7, 14, 21), five taps taken after 2, 7, 14, 21, 28 (64, 128, 256, 512, 512 channels, floor(H / 2^k) x floor(W / 2^k)),
+ * per tap n(f) = f / (sqrt(sum_c f^2) + 1e-10), d = sum_c w[c] (n(fa) - n(fb))^2, its mean over the tap's pixels; LPIPS is the sum of
+ * the five means.  The convolutions run as implicit GEMMs on the exact-fp32 MFMA (fmaf chains).  Images are 8-bit interleaved RGB,
+ * [F, H, W, 3] uint8.  H and W >= 16 (below, the fifth tap is empty), images x H x W x 64 below 2^31; a refused size, a NULL pointer
+ * or a workspace that is too small is HN_EINVAL with a message, before anything is launched.  hn_lpips and hn_lpips_features neither
+ * synchronise nor allocate, every reduction runs in a fixed order without floating-point atomics, and an image's values do not
+ * depend on the batch it is in: the same bits on every run and for every split of a batch.
+ *   hn_lpips_create (:28, the constructor of lpips.LPIPS): conv_weight, conv_bias: HOST arrays of 13 device pointers, fp32
+ *     [Cout, Cin, 3, 3] and [Cout] in torch's layout; lin_weight: a HOST array of 5 device pointers, fp32 [C].  Packs the weights into
+ *     one device allocation (hipMalloc) and synchronises the stream: the caller's tensors may go when it returns.
+ *   hn_lpips_destroy: hipFree (waits for the device); NULL is fine.
+ *   hn_lpips_workspace_bytes: the workspace of one hn_lpips call on F pairs, or one hn_lpips_features call on F images (0 for sizes
+ *     it refuses);
+ *   hn_lpips (:32-33, :44): per_tap [F, 5] fp64 = the five tap means of every pair (a[f], b[f]);
+ *   hn_lpips_features: the five taps of F images, fp32 [F, C, h, w] in torch's layout (the `outs` of lpips.LPIPS.forward). */
+typedef struct hn_lpips_model hn_lpips_model;  /* opaque: the packed weights of one LPIPS(VGG) model */
+int hn_lpips_create(const float* const* conv_weight, const float* const* conv_bias, const float* const* lin_weight, hn_lpips_model** out,
+                    hn_stream_t stream);
+int hn_lpips_destroy(hn_lpips_model* model);
+size_t hn_lpips_workspace_bytes(long long n_pairs, long long height, long long width);
+int hn_lpips(const hn_lpips_model* model, const unsigned char* a, const unsigned char* b, long long n_pairs, long long height, long long width,
+             double* per_tap, void* workspace, size_t workspace_bytes, hn_stream_t stream);
+int hn_lpips_features(const hn_lpips_model* model, const unsigned char* img, long long n_images, long long height, long long width, float* tap0,
+                      float* tap1, float* tap2, float* tap3, float* tap4, void* workspace, size_t workspace_bytes, hn_stream_t stream);
 
 #ifdef __cplusplus
 }
