@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "hn_common.h"
+#include "hn_mlp2.h"   // (v2::WG_SAMPLES, v2::XCD_PACE_MIN_ROUNDS: from which size the hand field kernel treats a launch as long)
 
 namespace hn {
 
@@ -302,9 +303,14 @@ __constant__ float c_cutoff_api[21] = {0.08f, 0.03f, 0.03f, 0.02f, 0.02f, 0.03f,
 // samples of one frame stay together and a wave's 32 samples share their pose except at the frame boundaries).
 // idx[k]: dense index of compact slot k; pos[i]: compact slot of sample i or -1.
 constexpr int COMPACT_SPB = 2048;
-// the classification of one sample: live unless every bone mask is certainly exactly 0
+// the classification of one sample: live unless every bone mask is certainly exactly 0.  dead_above: the value of 200 (v_b - cutoff_b)
+// beyond which a mask counts as 0 -- HAND_DEAD_ABOVE where a dead sample is NOT evaluated (the far-field skip: it must be certain),
+// HAND_FAR_ABOVE where the answer only decides a sample's PLACE in a launch that evaluates every sample (the live-first order)
+constexpr float HAND_DEAD_ABOVE = 20.f;
+constexpr float HAND_FAR_ABOVE = 17.f;
 __device__ __forceinline__ bool hand_sample_live(const float* __restrict__ pts, int i, const float* __restrict__ bt_inv,
-                                                 const float* __restrict__ T_pose, int n_frames, int pts_per_frame) {
+                                                 const float* __restrict__ T_pose, int n_frames, int pts_per_frame,
+                                                 float dead_above = HAND_DEAD_ABOVE) {
     const float p0 = pts[3 * (size_t)i], p1 = pts[3 * (size_t)i + 1], p2 = pts[3 * (size_t)i + 2];
     int frame = i / pts_per_frame;
     frame = frame < n_frames ? frame : n_frames - 1;
@@ -317,19 +323,19 @@ __device__ __forceinline__ bool hand_sample_live(const float* __restrict__ pts, 
         const float q1 = m[4] * p0 + m[5] * p1 + m[6] * p2 + m[7] - T[3 * b + 1];
         const float q2 = m[8] * p0 + m[9] * p1 + m[10] * p2 + m[11] - T[3 * b + 2];
         const float v = sqrtf(q0 * q0 + q1 * q1 + q2 * q2);
-        live = live || !(200.f * (v - c_cutoff_api[b]) > 20.f);   // (a NaN coordinate counts as live)
+        live = live || !(200.f * (v - c_cutoff_api[b]) > dead_above);   // (a NaN coordinate counts as live)
     }
     return live;
 }
 // pass 1 (one sample per thread): pos[i] = 1 (live) / 0, counts[u] = live samples of the 128-sample UNIT u (two per block)
 __global__ __launch_bounds__(256) void k_hand_live_count(const float* __restrict__ pts, int n, const float* __restrict__ bt_inv,
                                                          const float* __restrict__ T_pose, int n_frames, int pts_per_frame,
-                                                         int* __restrict__ pos, int* __restrict__ counts) {
+                                                         int* __restrict__ pos, int* __restrict__ counts, float dead_above) {
     __shared__ int wave_cnt[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
     bool live = false;
     if (i < n) {
-        live = hand_sample_live(pts, i, bt_inv, T_pose, n_frames, pts_per_frame);
+        live = hand_sample_live(pts, i, bt_inv, T_pose, n_frames, pts_per_frame, dead_above);
         pos[i] = live ? 1 : 0;
     }
     const int c = __popcll(__ballot(live));
@@ -490,6 +496,57 @@ __global__ __launch_bounds__(256) void k_hand_compact_write(const float* __restr
         }
     }
 }
+// ---- live-first order of a DENSE launch (render_single_impl) ------------------------------------------------
+// The same classification (at HAND_FAR_ABOVE: the kernel's own sigmoid is exactly 1 from 16.64) and the same per-unit counts as the
+// compaction, but nothing is left out: the ordered list holds all n
+// samples, [live samples, in dense order | far samples, in dense order], so that the waves of the field kernel are either all live
+// or all far instead of carrying a few live lanes each (a wave pays feature generation, stash round trips and the Jacobian
+// contraction for every bone that is live in ANY of its 32 lanes).  pos[i] >= 0 for every i, the launch is sized by n on the host.
+// A sample the predicate and the kernel's own mask disagree about sits in the "wrong" part and costs speed only: it is evaluated.
+//
+// pass 2 of 3 (one block): counts[u] -> the live samples in front of unit u (exclusive scan, in place); n_dev[0] = all live samples
+__global__ __launch_bounds__(1024) void k_hand_order_scan(int* __restrict__ counts, int n_units, int* __restrict__ n_dev) {
+    __shared__ int part[1024];
+    const int per = (n_units + 1023) / 1024;
+    const int u0 = threadIdx.x * per, u1 = u0 + per < n_units ? u0 + per : n_units;
+    int sum = 0;
+    for (int u = u0; u < u1; ++u) sum += counts[u];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {   // inclusive scan of the 1024 partial sums
+        const int v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - sum;
+    for (int u = u0; u < u1; ++u) {
+        const int c = counts[u];
+        counts[u] = run;
+        run += c;
+    }
+    if (threadIdx.x == 1023) n_dev[0] = part[1023];
+}
+// pass 3 of 3 (one sample per thread, two units per block as in k_hand_live_count): sample i with r live samples in front of it
+// goes to slot r if it is live, to slot n_live + (i - r) if it is far
+__global__ __launch_bounds__(256) void k_hand_order_write(const float* __restrict__ pts, int n, const int* __restrict__ scan,
+                                                          const int* __restrict__ n_dev, int* __restrict__ idx, int* __restrict__ pos,
+                                                          float* __restrict__ pts_c) {
+    __shared__ int wave_cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < n && pos[i] != 0;   // (k_hand_live_count's answer)
+    const unsigned long long m = __ballot(live);
+    if (lane == 0) wave_cnt[wave] = __popcll(m);
+    __syncthreads();
+    if (i >= n) return;
+    const int r = scan[2 * blockIdx.x + (wave >> 1)] + ((wave & 1) ? wave_cnt[wave - 1] : 0) + __popcll(m & ((1ull << lane) - 1ull));
+    const int k = live ? r : n_dev[0] + (i - r);
+    idx[k] = i;
+    pos[i] = k;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pts_c[3 * (size_t)k + c] = pts[3 * (size_t)i + c];
+}
 // compact results -> the dense per-sample arrays (dead samples: the far sample's values)
 __global__ void k_hand_scatter(const int* __restrict__ pos, int n, const int* __restrict__ n_dev, const float* __restrict__ sdf_c,
                                const float* __restrict__ grad_c, const float* __restrict__ rgb_c, float* __restrict__ sdf,
@@ -614,11 +671,27 @@ struct CompactRec {
 static int compact_hand(CompactRec& cr, const float* pts, int n, const float* bt_inv, const float* T_pose, int n_frames, int pts_per_frame,
                         hipStream_t s) {
     const int nb = (n + COMPACT_SPB - 1) / COMPACT_SPB;
-    hipLaunchKernelGGL(k_hand_live_count, dim3((n + 255) / 256), dim3(256), 0, s, pts, n, bt_inv, T_pose, n_frames, pts_per_frame, cr.pos, cr.counts);
+    hipLaunchKernelGGL(k_hand_live_count, dim3((n + 255) / 256), dim3(256), 0, s, pts, n, bt_inv, T_pose, n_frames, pts_per_frame, cr.pos, cr.counts,
+                       HAND_DEAD_ABOVE);
     hipLaunchKernelGGL(k_hand_compact_write, dim3(nb + 1), dim3(256), 0, s, pts, n, cr.counts, cr.idx, cr.pos, cr.pts_c, cr.n_dev, bt_inv, T_pose, n_frames,
                        pts_per_frame, CompactRec::aligned_frames(n, n_frames, pts_per_frame), cr.seg);
     HN_LAUNCH_CHECK();
     return HN_OK;
+}
+// the live-first order of ALL n samples of `pts` (one frame): cr.idx (ordered -> dense), cr.pos (dense -> ordered), cr.pts_c; cr.counts
+// holds the scan afterwards, cr.n_dev[0] the live count
+static int order_hand_live_first(CompactRec& cr, const float* pts, int n, const float* bt_inv, const float* T_pose, hipStream_t s) {
+    hipLaunchKernelGGL(k_hand_live_count, dim3((n + 255) / 256), dim3(256), 0, s, pts, n, bt_inv, T_pose, 1, n, cr.pos, cr.counts, HAND_FAR_ABOVE);
+    hipLaunchKernelGGL(k_hand_order_scan, dim3(1), dim3(1024), 0, s, cr.counts, (n + 127) / 128, cr.n_dev);
+    hipLaunchKernelGGL(k_hand_order_write, dim3((n + 255) / 256), dim3(256), 0, s, pts, n, cr.counts, cr.n_dev, cr.idx, cr.pos, cr.pts_c);
+    HN_LAUNCH_CHECK();
+    return HN_OK;
+}
+// HONERF_LIVE_FIRST, read per render call: 0 = off; unset or 1 = on for launches the field kernel treats as long; 2 = on at every size
+static int live_first_mode() {
+    const char* e = getenv("HONERF_LIVE_FIRST");
+    if (e == nullptr || e[0] == '\0') return 1;
+    return e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1);
 }
 
 // bump allocator over the caller's workspace
@@ -858,7 +931,9 @@ static int render_single_impl(const hn_field* f, const float* rays_o, const floa
     const bool may_compact = f->kind == HN_FIELD_HAND && f->compact_far_field;
     const size_t fws_bytes = field_ws(f, may_compact ? hand_cap(f, N) : (int)N);
     void* fws = ar.take(fws_bytes);
-    void* crec_ws = may_compact ? ar.take(CompactRec::bytes(N)) : nullptr;
+    // the dense final evaluation of an f16x3 / f16 hand field may run in live-first order (below): its record takes the same room
+    const bool may_order = f->kind == HN_FIELD_HAND && f->precision == HN_PREC_F16X3 && !may_compact;
+    void* crec_ws = (may_compact || may_order) ? ar.take(CompactRec::bytes(N)) : nullptr;
     if (need != nullptr) {
         *need = ar.used;
         return HN_OK;
@@ -970,6 +1045,21 @@ static int render_single_impl(const hn_field* f, const float* rays_o, const floa
         sdf = kp.sdf;
         grad = kp.grad;
         rgb = kp.rgb;
+    } else if (const int lf = may_order ? live_first_mode() : 0;
+               lf == 2 || (lf == 1 && (N + v2::WG_SAMPLES - 1) / v2::WG_SAMPLES >= (size_t)v2::XCD_PACE_MIN_ROUNDS * (size_t)cus_now)) {
+        // Live-first order: every sample is evaluated, by the same kernel in ONE launch -- on the list
+        // [live samples | far samples], each part in dense order -- and the outputs go back to dense order in front of alpha.  No result
+        // depends on which lane, wave or tile a sample sits in (tests/test_gpu_live_first_order.py).  Below XCD_PACE_MIN_ROUNDS tiles
+        // per CU -- the size from which the field kernel itself treats a launch as long -- the four small launches are not paid for.
+        CompactRec cr;
+        cr.at(crec_ws, N);
+        HN_TRY(order_hand_live_first(cr, t.pts, (int)N, bt_inv, T_pose, s));
+        set_launch_orig_idx(cr.idx);
+        const int rc = field_eval(f, cr.pts_c, rays_d, (int)N, S, bt_inv, T_pose, 1, hand_ppf, cr.sdf_c, cr.grad_c, cr.rgb_c, nullptr, fws, fws_bytes, s);
+        set_launch_orig_idx(nullptr);
+        HN_TRY(rc);
+        hipLaunchKernelGGL(k_hand_scatter, dim3(((int)N + 255) / 256), dim3(256), 0, s, cr.pos, (int)N, cr.n_dev, cr.sdf_c, cr.grad_c, cr.rgb_c, sdf, grad, rgb);
+        HN_LAUNCH_CHECK();
     } else {
         HN_TRY(field_eval(f, t.pts, rays_d, (int)N, S, bt_inv, T_pose, 1, hand_ppf, sdf, grad, rgb, nullptr, fws, fws_bytes, s));
     }
