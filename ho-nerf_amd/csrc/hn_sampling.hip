@@ -183,55 +183,14 @@ __global__ void k_sample_points(const float* __restrict__ o, const float* __rest
     for (int c = 0; c < 3; ++c) pts[3 * (size_t)i + c] = o[3 * b + c] + d[3 * b + c] * t;
 }
 
-// The same with V consecutive samples per thread when n % V == 0: 16-byte loads of z (+ the next depth), 16-byte stores of
-// pts (12 V consecutive bytes) and of dists, instead of 3 + 1 scalar stores at a 12-byte stride.
-// (tried and lost: streaming `nt` stores 0.36 of the HBM peak, 8 samples per thread 0.45 - 0.51, an output-major form
-// with perfectly coalesced stores but six integer divisions per thread 0.33 - 0.40)
-template <int V>   // V consecutive samples per thread (4 or 8), n % V == 0
-__global__ void k_sample_points_v(const float* __restrict__ o, const float* __restrict__ d, const float* __restrict__ z,
-                                  int n_rays, int n, int mid, float sample_dist, float* __restrict__ pts,
-                                  float* __restrict__ dists) {
-    const unsigned q = blockIdx.x * blockDim.x + threadIdx.x;   // group of V samples (32-bit index arithmetic: one
-    const unsigned total = (unsigned)n_rays * (unsigned)n / V;   // unsigned division per thread; the 64-bit form was
-    if (q >= total) return;                                      // a third of the kernel's time)
-    const unsigned i = q * V;
-    const int b = (int)(i / (unsigned)n), k = (int)(i - (unsigned)b * (unsigned)n);
-    float t[V];
-#pragma unroll
-    for (int v = 0; v < V / 4; ++v) {
-        const float4 zz = reinterpret_cast<const float4*>(z)[q * (V / 4) + v];
-        t[4 * v] = zz.x;
-        t[4 * v + 1] = zz.y;
-        t[4 * v + 2] = zz.z;
-        t[4 * v + 3] = zz.w;
-    }
-    if (mid) {
-        float dd[V];
-#pragma unroll
-        for (int j = 0; j + 1 < V; ++j) dd[j] = t[j + 1] - t[j];
-        dd[V - 1] = (k + V < n) ? z[i + V] - t[V - 1] : sample_dist;
-#pragma unroll
-        for (int v = 0; v < V / 4; ++v)
-            reinterpret_cast<float4*>(dists)[q * (V / 4) + v] = make_float4(dd[4 * v], dd[4 * v + 1], dd[4 * v + 2], dd[4 * v + 3]);
-#pragma unroll
-        for (int j = 0; j < V; ++j) t[j] = t[j] + dd[j] * 0.5f;
-    }
-    const float ox = o[3 * b], oy = o[3 * b + 1], oz = o[3 * b + 2], dx = d[3 * b], dy = d[3 * b + 1], dz = d[3 * b + 2];
-    float p[3 * V];
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-        p[3 * j] = ox + dx * t[j];
-        p[3 * j + 1] = oy + dy * t[j];
-        p[3 * j + 2] = oz + dz * t[j];
-    }
-    float4* out = reinterpret_cast<float4*>(pts) + (3 * V / 4) * q;
-#pragma unroll
-    for (int v = 0; v < 3 * V / 4; ++v) out[v] = make_float4(p[4 * v], p[4 * v + 1], p[4 * v + 2], p[4 * v + 3]);
-}
-
-// 4 samples per thread with the 48 bytes of points a thread produces TRANSPOSED through a wave-private LDS region, so that every
-// store instruction of a wave writes 1 KiB of consecutive bytes (as 3 float4 per lane at a 48-byte stride each instruction
-// touches every cache line of the wave's 3 KiB and fills a third of it).  No barrier: a wave's LDS operations complete in order.
+// The same with 4 consecutive samples per thread when n % 4 == 0 and z, pts and dists are 16-byte aligned: a 16-byte load of z
+// (+ the next depth) and a 16-byte store of dists, instead of scalar accesses; 32-bit index arithmetic (one unsigned division per
+// thread: the 64-bit form was a third of the kernel's time).  The 48 bytes of points a thread produces are TRANSPOSED through a
+// wave-private LDS region, so that every store instruction of a wave writes 1 KiB of consecutive bytes (as 3 float4 per lane at a
+// 48-byte stride each instruction touches every cache line of the wave's 3 KiB and fills a third of it).  No barrier: a wave's
+// LDS operations complete in order.
+// (tried and lost: the strided float4 stores without the transpose, streaming `nt` stores 0.36 of the HBM peak, 8 samples per
+// thread 0.45 - 0.51, an output-major form with perfectly coalesced stores but six integer divisions per thread 0.33 - 0.40)
 __global__ __launch_bounds__(256) void k_sample_points_t(const float* __restrict__ o, const float* __restrict__ d, const float* __restrict__ z,
                                                          int n_rays, int n, int mid, float sample_dist, float* __restrict__ pts,
                                                          float* __restrict__ dists) {

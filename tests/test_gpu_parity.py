@@ -142,7 +142,6 @@ def test_coarse_z_and_points(L):
     dists = torch.empty(B * 40, device='cuda')
     sd = (1.5 - 0.4) / 40
     L.check(lib.hn_sample_points(L.ptr(cu(o)), L.ptr(cu(d)), L.ptr(z), B, 40, 1, sd, L.ptr(pts), L.ptr(dists), st()), 'pts')
-    mid, dr = orr.mid_points(ref, sd)
     mid, dr = orr.mid_points(z.cpu(), sd)
     assert np.array_equal(dists.cpu().numpy().reshape(B, 40), dr.numpy())
     assert_close(pts, orr._pts(o, d, mid).reshape(-1, 3), 1e-6, 'mid points')
