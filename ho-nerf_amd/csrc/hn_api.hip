@@ -693,6 +693,12 @@ static int live_first_mode() {
     if (e == nullptr || e[0] == '\0') return 1;
     return e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1);
 }
+// HONERF_UNIFORM_STASH, read per hand-field launch (hn_field2_hand.hip, Hand2Args::ustash): 0 = full-width stash traffic in every wave;
+// unset or 1 = a wave whose 32 samples are all far stores and reads ONE column per half (the same bits: DESIGN.md 3.1)
+int uniform_stash_mode() {
+    const char* e = getenv("HONERF_UNIFORM_STASH");
+    return (e != nullptr && e[0] == '0') ? 0 : 1;
+}
 
 // bump allocator over the caller's workspace
 struct Arena {

@@ -65,6 +65,8 @@ struct Hand2Args {
     float4* scratch;
     int dbg;
     int cull;   // hn_field_set_culling
+    int ustash; // HONERF_UNIFORM_STASH (hn_api.hip: uniform_stash_mode), the full evaluation (MODE 1) only: a wave whose samples are all far
+                // moves one column of its stash per half instead of 32.  Holds StashT::umask of such a wave: USTASH_COLS (on) or 0 (off)
     // adjoint (MODE 2): upstream gradients in, input / pose gradients out
     const float* g_sdf;    // [n]
     const float* g_grad;   // [n,3]
@@ -115,6 +117,7 @@ enum {
     HAND2_SLOTS_ADJ = 41,
 };
 constexpr int FEAT_BLOCKS = 4 * N_BONES;     // first leftover block index
+constexpr int USTASH_COLS = 0x1f0;           // the sample-column bits of lane * 16 (StashT::umask of a uniform wave)
 constexpr int STAGE_BYTES = 8 * 1024;        // LDS staging of one bone's 4 fragment pairs (Jacobian pass)
 constexpr int POSE_ROW = 256;                // floats per wave and frame: 21 bones x 12 pose-gradient addends (Hand2Args::pose_part)
 constexpr int POSE_FRAMES = 2;               // frames a WAVE may touch for the atomics-free pose gradients: its first sample's and the next
@@ -412,7 +415,14 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
 #define HN_ADJ_WB 0   // (A/B, round 4: write-back stores for the adjoint kernel's w_l tiles too, in the hope that the second reverse sweep
                       //  finds them in L2 / MALL: k_field2_hand<4> 0.933 -> 0.971 ms.  nt stays.)
 #endif
-    StashT<(MODE <= 1 || (HN_ADJ_WB && MODE >= 4)) ? STASH_ST_AUX : STASH_AUX> sh;   // (evaluation kernels: write-back stores; taped / adjoint kernels: nt -- hn_mlp2.h)
+    // USTASH (the full evaluation on the 32x32x16 shape, where lane = (sample column j, half h)): a wave with nz == 0 -- no sample has a
+    // non-zero bone mask -- has 1386 features of exactly 0, zero B fragments in lin0 and in the lin4 skip, and therefore the SAME numbers,
+    // bit for bit, in every sample column of a1..a7, dz7, the feature vector and dz4.  Its MFMAs all run (dense compute); its stash traffic
+    // is one column per half: the lanes with j == 0 store, every lane reads the column of lane 32 h (StashT<.., UNI>, a lane offset and no
+    // branch).  A wave with any live lane, the sdf-only kernel and every taped / adjoint mode (their tape is read by other launches)
+    // move the stash at full width.
+    constexpr bool USTASH = MODE == 1 && !S16;
+    StashT<(MODE <= 1 || (HN_ADJ_WB && MODE >= 4)) ? STASH_ST_AUX : STASH_AUX, USTASH> sh;   // (evaluation kernels: write-back stores; taped / adjoint kernels: nt -- hn_mlp2.h)
     sh.init(a.scratch + ((size_t)blockIdx.x * WG_WAVES + wave) * N_SLOTS * SLOT_F4, N_SLOTS, lane);
     constexpr int FEAT = HS_FEAT * SLOT_BYTES;   // byte offset of the feature fragment blocks
     constexpr int LEFT = HS_LEFT * SLOT_BYTES;   // ... of the leftover values
@@ -479,6 +489,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         // consumers substitute zero fragments instead of loading (the MFMAs still run: dense compute).
         ws.stamp(7);   // (points and frame known)
         unsigned nz = 0;
+        if constexpr (USTASH) sh.umask = 0;   // (the live bones' fragments below are stored before the wave knows what it is)
         if constexpr (!RUN_FWD) {
             nz = __builtin_bit_cast(unsigned, sh.f32_load(NZ_OFF));   // as the evaluation launch left it
         } else {
@@ -504,6 +515,11 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             sh.f32_store(LEFT + b * 256, any ? (h ? bn.r[2] : bn.r[1]) * bn.hh : 0.f);
         }
         nz = __builtin_amdgcn_readfirstlane(nz);
+        // from here to the end of the tile a uniform wave moves one stash column per half (the 21 leftover values above are stored at full
+        // width: the wave is not known to be uniform before its last bone; they are all +0 and are not read back)
+        // (the mask value comes from the host: formed here from a flag, the flag's test is hoisted out of the tile loop as a lane mask, and
+        //  the first feature pass's load_bone(0) ends up with waits in its zero arm -- tests/test_abi.py's static check of the ISA)
+        if constexpr (USTASH) sh.umask = nz == 0u ? a.ustash : 0;
         ws.stamp(8);   // (bone loop of the feature generation done)
         {   // leftover block: element j of k-step u belongs to bone 8u + j
             h8 fh[4], fl[4];
@@ -511,7 +527,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             for (int u = 0; u < 4; ++u) {
                 float f[8];
 #pragma unroll
-                for (int jj = 0; jj < 8; ++jj) f[jj] = (u < 3 && 8 * u + jj < N_BONES) ? sh.f32_load(LEFT + (8 * u + jj) * 256) : 0.f;
+                for (int jj = 0; jj < 8; ++jj) f[jj] = (u < 3 && 8 * u + jj < N_BONES) ? sh.f32_load_z(LEFT + (8 * u + jj) * 256) : 0.f;
                 split8(f, fh[u], fl[u]);
             }
 #pragma unroll
@@ -1356,6 +1372,7 @@ int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const flo
     a.grad = grad;
     a.rgb = rgb;
     a.feat = feat;
+    a.ustash = (full && uniform_stash_mode()) ? USTASH_COLS : 0;   // (the full evaluation kernels alone are built with it)
 #ifdef HN_DEBUG_HOOKS
     {
         const char* e = getenv("HN_DBG");

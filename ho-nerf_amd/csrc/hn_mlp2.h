@@ -1092,14 +1092,22 @@ constexpr int STASH_AUX = HN_STASH_AUX;
 #define HN_STASH_ST_AUX 0
 #endif
 constexpr int STASH_ST_AUX = HN_STASH_ST_AUX;
-template <int ST_AUX>
+// UNI (the hand evaluation kernel, hn_field2_hand.hip): the stash of a wave whose 32 sample columns hold the same numbers bit for bit
+// can be moved as ONE column per half.  `umask` is wave-uniform (an SGPR): 0 = every lane stores and reads its own 16 bytes, as without
+// UNI; 0x1f0 (the column bits j of lane * 16 = 512 h + 16 j) = only the two lanes with j == 0 store, at the addresses they always use,
+// and every lane reads the address of lane 32 h.  No branch: a lane that does not store gets an offset beyond the descriptor's range
+// (the hardware drops the store, as for the absent pieces of WStream::piece), a load masks the column bits away.  Both offsets are
+// formed from lane_x16() at the point of use, for the reason given above fresh_voff().
+template <int ST_AUX, bool UNI = false>
 struct StashT {
     __amdgpu_buffer_rsrc_t rsrc;
     int voff;   // lane * 16
+    int umask;  // UNI: 0 or 0x1f0, wave-uniform
 
     __device__ __forceinline__ void init(float4* wave_base, int n_slots, int lane) {
         rsrc = __builtin_amdgcn_make_buffer_rsrc(wave_base, 0, n_slots * SLOT_BYTES, 0x00020000);
         voff = lane * 16;
+        umask = 0;
     }
     // 16-byte store.  The byte offset goes into the VGPR operand and soffset stays 0 on purpose: with an
     // SGPR soffset hipcc (ROCm 7.2) places no wait state between a buffer_store_dwordx4 and a following
@@ -1111,7 +1119,21 @@ struct StashT {
     // (lane * 16 + constant), and hoisted out of the persistent tile loop -- as LICM does with plain arithmetic --
     // the few hundred of them are all live across the whole kernel, get spilled at its top and are re-read from
     // scratch memory in front of every stash store (measured: 568 scratch loads in the full object kernel).
-    __device__ __forceinline__ int fresh_voff() const { return lane_x16(); }
+    // (UNI: lane * 16 + (column bits << 20) -- at least 16 MiB, beyond any stash, for the lanes of a uniform wave that do not store)
+    __device__ __forceinline__ int fresh_voff() const {
+        if constexpr (UNI) {
+            const int l16 = lane_x16();
+            return l16 + ((l16 & umask) << 20);
+        } else
+            return lane_x16();
+    }
+    // the lane offset of a 16-byte LOAD (UNI, uniform wave: the column of lane 32 h, i.e. (lane & 32) * 16)
+    __device__ __forceinline__ int load_voff() const {
+        if constexpr (UNI)
+            return lane_x16() & ~umask;
+        else
+            return lane_x16();
+    }
     template <typename T16>
     __device__ __forceinline__ void st16_at(const T16& v, int vo) const {
         static_assert(sizeof(T16) == 16, "16-byte values only");
@@ -1136,7 +1158,7 @@ struct StashT {
         using f32x4 = float __attribute__((ext_vector_type(4)));
         using f32x8 = float __attribute__((ext_vector_type(8)));
         const int off = slot * SLOT_BYTES + t * 4096;
-        const int vo = lane_x16();
+        const int vo = load_voff();
         const f32x4 a = __builtin_bit_cast(f32x4, ld16_at(vo, off));
         const f32x4 b = __builtin_bit_cast(f32x4, ld16_at(vo, off + 1024));
         const f32x4 c = __builtin_bit_cast(f32x4, ld16_at(vo, off + 2048));
@@ -1160,7 +1182,7 @@ struct StashT {
     }
     __device__ __forceinline__ f32x16 tile_load_half(int slot, int t) const {
         const int off = slot * SLOT_BYTES + t * 4096;
-        const int vo = lane_x16();
+        const int vo = load_voff();
         const h8 a = __builtin_bit_cast(h8, ld16_at(vo, off));
         const h8 b = __builtin_bit_cast(h8, ld16_at(vo, off + 1024));
         f32x16 y;
@@ -1178,7 +1200,7 @@ struct StashT {
         st16_at(lo, vo + 1024);
     }
     __device__ __forceinline__ void frag_load(int base, int s, h8& hi, h8& lo) const {
-        const int vo = lane_x16();
+        const int vo = load_voff();
         const u32x4 a = ld16_at(vo, base + s * KS_BYTES);
         const u32x4 b = ld16_at(vo, base + s * KS_BYTES + 1024);
         hi = __builtin_bit_cast(h8, a);
@@ -1190,6 +1212,14 @@ struct StashT {
     }
     __device__ __forceinline__ float f32_load(int off) const {
         return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, lane_x16() >> 2, off, 0));
+    }
+    // the same for a value that is known to be +0 in every lane of a uniform wave (UNI, umask != 0): there the offset lies beyond the
+    // descriptor's range, the load moves nothing and returns 0
+    __device__ __forceinline__ float f32_load_z(int off) const {
+        if constexpr (UNI)
+            return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, (lane_x16() >> 2) + (umask << 20), off, 0));
+        else
+            return f32_load(off);
     }
 };
 using Stash = StashT<STASH_AUX>;   // (the taped kernels and every kernel that did not ask for another policy)
