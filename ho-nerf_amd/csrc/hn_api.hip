@@ -694,10 +694,12 @@ static int live_first_mode() {
     return e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1);
 }
 // HONERF_UNIFORM_STASH, read per hand-field launch (hn_field2_hand.hip, Hand2Args::ustash): 0 = full-width stash traffic in every wave;
-// unset or 1 = a wave whose 32 samples are all far stores and reads ONE column per half (the same bits: DESIGN.md 3.1)
+// 2 = a wave whose 32 samples are all far stores and reads ONE column per half, at the addresses its lanes 0 and 32 always used;
+// unset or 1 = the same column packed into whole 128-byte lines of the wave's free slot (the same bits in all three: DESIGN.md 3.1)
 int uniform_stash_mode() {
     const char* e = getenv("HONERF_UNIFORM_STASH");
-    return (e != nullptr && e[0] == '0') ? 0 : 1;
+    if (e == nullptr) return 1;
+    return e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1);
 }
 
 // bump allocator over the caller's workspace

@@ -54,7 +54,8 @@ bool launch_three_pass();         // hn_api.hip: inside a render that keeps a TA
                                   // render of such a field is the HN_PREC_F16X3 field's, bit for bit
 int quad_max_blocks_override();   // hn_debug_quad_max_blocks: -1 = default selection of the latency-form kernels
 int uniform_stash_mode();         // hn_api.hip: HONERF_UNIFORM_STASH, read per launch (Hand2Args::ustash): 0 = every wave of the hand evaluation
-                                  // kernel moves its stash at full width; unset or 1 = a wave whose samples are all far keeps one column
+                                  // kernel moves its stash at full width; 2 = a wave whose samples are all far keeps one column, in
+                                  // place; unset or 1 = that column packed into whole cache lines
 int pace_phantom_members();    // hn_debug_pace_phantom: members that never arrive at the XCD meetings (timeout-path test hook), 0 = off
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): `mask` is the kernel's own
 // bit set of devices already configured (a static std::atomic<uint64_t> next to the launch).

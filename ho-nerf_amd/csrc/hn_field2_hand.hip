@@ -66,7 +66,8 @@ struct Hand2Args {
     int dbg;
     int cull;   // hn_field_set_culling
     int ustash; // HONERF_UNIFORM_STASH (hn_api.hip: uniform_stash_mode), the full evaluation (MODE 1) only: a wave whose samples are all far
-                // moves one column of its stash per half instead of 32.  Holds StashT::umask of such a wave: USTASH_COLS (on) or 0 (off)
+                // moves one column of its stash per half instead of 32.  Holds StashT::umask of such a wave, USTASH_COLS, plus -- packed
+                // form -- StashT::ush in its low four bits (USTASH_SHIFT); 0 = off
     // adjoint (MODE 2): upstream gradients in, input / pose gradients out
     const float* g_sdf;    // [n]
     const float* g_grad;   // [n,3]
@@ -99,7 +100,7 @@ enum {
     HS_DZ7 = 7,     // fragments
     HS_FVEC = 8,    // fragments
     HS_DZ4 = 9,     // fragments
-    HS_A4F = 10,    // (free: a4 used to pass through here as fragments)
+    HS_A4F = 10,    // the packed stash image of a uniform wave (USTASH_REGION below); no other use: a4 used to pass through here as fragments
     HS_FEAT = 11,   // 87 k-step blocks of feature fragments (84 bone + 3 leftover) = 174 KiB -> 6 slots
     HS_LEFT = 17,   // 21 x 64 floats: the leftover (r_1 | r_2) h values while the bones are generated
     HAND2_SLOTS = 18,
@@ -118,6 +119,24 @@ enum {
 };
 constexpr int FEAT_BLOCKS = 4 * N_BONES;     // first leftover block index
 constexpr int USTASH_COLS = 0x1f0;           // the sample-column bits of lane * 16 (StashT::umask of a uniform wave)
+// The packed image of a uniform wave's stash (StashT, hn_mlp2.h: 32 bytes per 1 KiB instruction block) lies in slot HS_A4F of the wave's own
+// region, which nothing else stores to or loads from in the evaluation kernels: neither what the same tile stores in the normal layout
+// before the wave knows that it is uniform (the 21 HS_LEFT values, a live bone's HS_FEAT blocks) nor any normal-layout access of the tile
+// before or the tile after on this workgroup (the stash is per workgroup and reused tile after tile) shares an address with the image,
+// so there is nothing to order between the two layouts.  Image against image, tile after tile, is the reuse every slot always had: a
+// tile's loads have returned before the values that the next tile stores exist.
+constexpr int USTASH_REGION = HS_A4F * SLOT_BYTES;
+static_assert(USTASH_REGION == (USTASH_SHIFT << 16) && (USTASH_COLS & 15) == 0 && USTASH_SHIFT < 16,
+              "the kernel forms StashT::ubase as ush << 16 and takes ush from the low four bits of Hand2Args::ustash");
+// every UNI site of the kernel, as 1 KiB blocks of the wave's region: the fp32 tiles a1..a7 (8 tiles x 4 instructions per slot), the 16
+// [hi | lo] fragment blocks of HS_DZ7, HS_FVEC and HS_DZ4, and the three leftover feature blocks behind the 84 bone blocks of HS_FEAT
+// (192 bytes: the one line of the image that is half used).  The list is kept by hand: it has to follow the sh.tile_* / sh.frag_* calls
+// of the MODE 1 body.  One access is outside it on purpose: load_bone(N_BONES) reads four blocks, and the fourth (block 87) is stored by
+// nobody in either layout -- its fragments feed no MFMA (KS_LEFT = 3).  Packed, that load lands at region + 16 832, inside the slot, on
+// a cell of the image's last line that no site owns.
+constexpr int USTASH_SITES[][2] = {{HS_A1 * 32, 7 * 32}, {HS_DZ7 * 32, 32}, {HS_FVEC * 32, 32}, {HS_DZ4 * 32, 32}, {HS_FEAT * 32 + 2 * 4 * N_BONES, 2 * 3}};
+static_assert(ustash_map_ok(USTASH_REGION, SLOT_BYTES, USTASH_SITES, 5, 1),
+              "the packed stash image must be injective, stay inside slot HS_A4F and fill the lines it touches");
 constexpr int STAGE_BYTES = 8 * 1024;        // LDS staging of one bone's 4 fragment pairs (Jacobian pass)
 constexpr int POSE_ROW = 256;                // floats per wave and frame: 21 bones x 12 pose-gradient addends (Hand2Args::pose_part)
 constexpr int POSE_FRAMES = 2;               // frames a WAVE may touch for the atomics-free pose gradients: its first sample's and the next
@@ -419,8 +438,9 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
     // non-zero bone mask -- has 1386 features of exactly 0, zero B fragments in lin0 and in the lin4 skip, and therefore the SAME numbers,
     // bit for bit, in every sample column of a1..a7, dz7, the feature vector and dz4.  Its MFMAs all run (dense compute); its stash traffic
     // is one column per half: the lanes with j == 0 store, every lane reads the column of lane 32 h (StashT<.., UNI>, a lane offset and no
-    // branch).  A wave with any live lane, the sdf-only kernel and every taped / adjoint mode (their tape is read by other launches)
-    // move the stash at full width.
+    // branch) -- by default packed into whole 128-byte lines of the wave's free slot (USTASH_REGION above), 10.2 KiB each way per tile
+    // instead of 640 lines touched for as much.  A wave with any live lane, the sdf-only kernel and every taped / adjoint mode (their
+    // tape is read by other launches) move the stash at full width.
     constexpr bool USTASH = MODE == 1 && !S16;
     StashT<(MODE <= 1 || (HN_ADJ_WB && MODE >= 4)) ? STASH_ST_AUX : STASH_AUX, USTASH> sh;   // (evaluation kernels: write-back stores; taped / adjoint kernels: nt -- hn_mlp2.h)
     sh.init(a.scratch + ((size_t)blockIdx.x * WG_WAVES + wave) * N_SLOTS * SLOT_F4, N_SLOTS, lane);
@@ -489,7 +509,10 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         // consumers substitute zero fragments instead of loading (the MFMAs still run: dense compute).
         ws.stamp(7);   // (points and frame known)
         unsigned nz = 0;
-        if constexpr (USTASH) sh.umask = 0;   // (the live bones' fragments below are stored before the wave knows what it is)
+        if constexpr (USTASH) {   // (the live bones' fragments below are stored before the wave knows what it is)
+            sh.umask = 0;
+            sh.set_packed(0, 0);
+        }
         if constexpr (!RUN_FWD) {
             nz = __builtin_bit_cast(unsigned, sh.f32_load(NZ_OFF));   // as the evaluation launch left it
         } else {
@@ -519,7 +542,12 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         // width: the wave is not known to be uniform before its last bone; they are all +0 and are not read back)
         // (the mask value comes from the host: formed here from a flag, the flag's test is hoisted out of the tile loop as a lane mask, and
         //  the first feature pass's load_bone(0) ends up with waits in its zero arm -- tests/test_abi.py's static check of the ISA)
-        if constexpr (USTASH) sh.umask = nz == 0u ? a.ustash : 0;
+        //  -- and so do the shift and the region of the packed form, by arithmetic on that value)
+        if constexpr (USTASH) {
+            const int us = nz == 0u ? a.ustash : 0;
+            sh.umask = us & USTASH_COLS;
+            sh.set_packed(us & 15, (us & 15) << 16);
+        }
         ws.stamp(8);   // (bone loop of the feature generation done)
         {   // leftover block: element j of k-step u belongs to bone 8u + j
             h8 fh[4], fl[4];
@@ -645,9 +673,18 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
 #define HN_DBG_NO_FEAT_LOADS 0   // 1 (measurement only, WRONG results): the feature passes never read the bones' fragments back from the stash -- an
                                  // upper bound on what reading them twice instead of four times could buy (round 5, profiles/r05/README.md)
 #endif
-        auto bone_loads = [&](int b) { return !HN_DBG_NO_FEAT_LOADS && (b >= N_BONES || ((nz >> b) & 1u)); };   // load_bone issues its 8 loads
+        auto bone_loads = [&](int b) { return !HN_DBG_NO_FEAT_LOADS && (USTASH || b >= N_BONES || ((nz >> b) & 1u)); };   // load_bone issues its 8 loads
         auto load_bone = [&](int b, h8(&oh)[4], h8(&ol)[4]) {
-            if (!HN_DBG_NO_FEAT_LOADS && (b >= N_BONES || ((nz >> b) & 1u))) {
+            if constexpr (USTASH) {
+                // No branch here: the fragments of a bone that is not live are LOADED from beyond the descriptor's range, which moves
+                // nothing and returns zeros (as f32_load_z).  As the two arms of a branch, the zero arm of the first feature pass's
+                // load_bone(0) comes out behind the loads with waits for them in front of its moves (tests/test_abi.py's static check
+                // of the ISA), and a uniform wave, which always takes it, then waits for the weight pieces in flight.
+                const unsigned live = HN_DBG_NO_FEAT_LOADS ? 0u : (((nz | (1u << N_BONES)) >> b) & 1u);
+                const int beyond = (int)((live ^ 1u) << 30);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) sh.frag_load(feat_base, 4 * b + s, oh[s], ol[s], beyond);
+            } else if (!HN_DBG_NO_FEAT_LOADS && (b >= N_BONES || ((nz >> b) & 1u))) {
 #pragma unroll
                 for (int s = 0; s < 4; ++s) sh.frag_load(feat_base, 4 * b + s, oh[s], ol[s]);
             } else {
@@ -1372,7 +1409,8 @@ int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const flo
     a.grad = grad;
     a.rgb = rgb;
     a.feat = feat;
-    a.ustash = (full && uniform_stash_mode()) ? USTASH_COLS : 0;   // (the full evaluation kernels alone are built with it)
+    const int us_mode = full ? uniform_stash_mode() : 0;   // (the full evaluation kernels alone are built with it)
+    a.ustash = us_mode == 0 ? 0 : (us_mode == 2 ? USTASH_COLS : (USTASH_COLS | USTASH_SHIFT));
 #ifdef HN_DEBUG_HOOKS
     {
         const char* e = getenv("HN_DBG");

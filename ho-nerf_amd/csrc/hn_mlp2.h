@@ -1098,17 +1098,69 @@ constexpr int STASH_ST_AUX = HN_STASH_ST_AUX;
 // and every lane reads the address of lane 32 h.  No branch: a lane that does not store gets an offset beyond the descriptor's range
 // (the hardware drops the store, as for the absent pieces of WStream::piece), a load masks the column bits away.  Both offsets are
 // formed from lane_x16() at the point of use, for the reason given above fresh_voff().
+// PACKED form of a uniform wave (`ush` = USTASH_SHIFT, `ubase` = the kernel's packed region; both 0 otherwise): left in place, the one
+// column is 16 useful bytes per half in every 1 KiB instruction block -- two 128-byte lines touched for 32 bytes.  Packed, block k
+// (byte offset 1024 k of the wave's region) becomes the 32 bytes [half 0 | half 1] at ubase + 32 k: the four instructions of a
+// tile_store / tile_load are ONE 128-byte line, the [hi | lo] pair of a fragment block is half a line.  The map is ustash_packed()
+// below; the code forms it as (offset >> ush) + ubase for the block (scalar) and lane offset >> ush for the half, so that the same
+// instructions serve all three forms without a branch and a wave with umask == 0 computes the addresses it always did.  The
+// instructions' immediate offsets (+ 1024 q) cannot follow a run-time stride: in a UNI kernel each 16-byte access gets its own offset.
+constexpr int USTASH_SHIFT = 5;   // 1 KiB block -> 32 bytes
+constexpr int ustash_packed(int region, int off, int half) { return region + (off >> USTASH_SHIFT) + ((512 * half) >> USTASH_SHIFT); }
+// The UNI sites of a kernel as whole 1 KiB blocks [first, first + count) of the wave's region (`sites`: n pairs).  True if the packed
+// image is injective, lies inside [region, region + region_bytes), starts on a line, and fills every 128-byte line it touches except
+// for `partial_lines` of them (a site whose blocks are no multiple of four).
+constexpr bool ustash_map_ok(int region, int region_bytes, const int (*sites)[2], int n, int partial_lines) {
+    constexpr int MAX_CELLS = 4096;   // 16-byte cells of the largest region checked (64 KiB)
+    if (region % 128 != 0 || region_bytes > MAX_CELLS * 16) return false;
+    bool seen[MAX_CELLS] = {};
+    for (int i = 0; i < n; ++i)
+        for (int k = sites[i][0]; k < sites[i][0] + sites[i][1]; ++k)
+            for (int half = 0; half < 2; ++half) {
+                const int p = ustash_packed(region, 1024 * k, half) - region;
+                if (p < 0 || p + 16 > region_bytes || p % 16 != 0 || seen[p / 16]) return false;
+                seen[p / 16] = true;
+            }
+    int partial = 0;
+    for (int line = 0; line < MAX_CELLS / 8; ++line) {
+        int used = 0;
+        for (int c = 0; c < 8; ++c) used += seen[8 * line + c] ? 1 : 0;
+        if (used != 0 && used != 8) ++partial;
+    }
+    return partial == partial_lines;
+}
 template <int ST_AUX, bool UNI = false>
 struct StashT {
     __amdgpu_buffer_rsrc_t rsrc;
     int voff;   // lane * 16
     int umask;  // UNI: 0 or 0x1f0, wave-uniform
+    int ush;    // UNI, packed form of a uniform wave: USTASH_SHIFT, else 0 (wave-uniform)
+    int ubase;  // ... and the byte offset of the wave's packed region, else 0
+    int ush_ld, ubase_ld;   // the same two numbers for the loads (set_packed)
 
     __device__ __forceinline__ void init(float4* wave_base, int n_slots, int lane) {
         rsrc = __builtin_amdgcn_make_buffer_rsrc(wave_base, 0, n_slots * SLOT_BYTES, 0x00020000);
         voff = lane * 16;
         umask = 0;
+        set_packed(0, 0);
     }
+    // UNI: where the 1 KiB block at byte offset `off` of the wave's region lies (ustash_packed for a packed wave, `off` itself otherwise).
+    // The loads take the two numbers from a copy that the compiler has to treat as unrelated (set_packed, once per tile): formed from the
+    // same values, the few hundred block offsets of a tile are common subexpressions of their store and their load, all live across the
+    // tile in scalar registers that the kernel does not have (measured: 72 more lane spills of scalars, 11 more scratch loads).
+    __device__ __forceinline__ void set_packed(int shift, int base) {
+        ush = shift;
+        ubase = base;
+        ush_ld = shift;
+        ubase_ld = base;
+        if constexpr (UNI) asm volatile("" : "+s"(ush_ld), "+s"(ubase_ld));
+    }
+    struct U {
+        int sh, base;
+        __device__ __forceinline__ int operator()(int off) const { return (off >> sh) + base; }
+        __device__ __forceinline__ int step() const { return 1024 >> sh; }   // from one 1 KiB block to the next
+    };
+    __device__ __forceinline__ U st_offs() const { return U{ush, ubase}; }
     // 16-byte store.  The byte offset goes into the VGPR operand and soffset stays 0 on purpose: with an
     // SGPR soffset hipcc (ROCm 7.2) places no wait state between a buffer_store_dwordx4 and a following
     // VALU write of its data registers (it assumes the hardware interlocks), and on gfx950 the store then
@@ -1119,18 +1171,19 @@ struct StashT {
     // (lane * 16 + constant), and hoisted out of the persistent tile loop -- as LICM does with plain arithmetic --
     // the few hundred of them are all live across the whole kernel, get spilled at its top and are re-read from
     // scratch memory in front of every stash store (measured: 568 scratch loads in the full object kernel).
-    // (UNI: lane * 16 + (column bits << 20) -- at least 16 MiB, beyond any stash, for the lanes of a uniform wave that do not store)
+    // (UNI: lane * 16 + (column bits << 20) -- at least 16 MiB, beyond any stash, for the lanes of a uniform wave that do not store;
+    //  packed: lane 32 h's 512 h becomes 16 h)
     __device__ __forceinline__ int fresh_voff() const {
         if constexpr (UNI) {
             const int l16 = lane_x16();
-            return l16 + ((l16 & umask) << 20);
+            return (l16 >> ush) + ((l16 & umask) << 20);
         } else
             return lane_x16();
     }
-    // the lane offset of a 16-byte LOAD (UNI, uniform wave: the column of lane 32 h, i.e. (lane & 32) * 16)
+    // the lane offset of a 16-byte LOAD (UNI, uniform wave: the column of lane 32 h, i.e. (lane & 32) * 16; packed: its 16 h)
     __device__ __forceinline__ int load_voff() const {
         if constexpr (UNI)
-            return lane_x16() & ~umask;
+            return (lane_x16() & ~umask) >> ush;
         else
             return lane_x16();
     }
@@ -1145,9 +1198,34 @@ struct StashT {
     }
     __device__ __forceinline__ u32x4 ld16_at(int vo, int off) const { return __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, off, STASH_AUX); }
     __device__ __forceinline__ u32x4 ld16(int off) const { return ld16_at(lane_x16(), off); }
+    // the scalar offsets of the 16-byte loads of one access: ld_offs()(off)
+    struct Same {
+        __device__ __forceinline__ int operator()(int off) const { return off; }
+        __device__ __forceinline__ int step() const { return 1024; }
+    };
+    __device__ __forceinline__ auto ld_offs() const {
+        if constexpr (UNI)
+            return U{ush_ld, ubase_ld};
+        else
+            return Same{};
+    }
     // fp32 tile t of slot `slot`: [t][q][lane] float4
     __device__ __forceinline__ void tile_store(int slot, int t, const f32x16& y) const {
         using f32x4 = float __attribute__((ext_vector_type(4)));
+        if constexpr (UNI) {
+            // (one offset register, stepped from store to store: four of them at once cost the epilogues registers they do not have)
+            const U u = st_offs();
+            const int step = u.step();
+            int vo = fresh_voff() + u(slot * SLOT_BYTES + t * 4096);
+            st16_at((f32x4)__builtin_shufflevector(y, y, 0, 1, 2, 3), vo);
+            vo += step;
+            st16_at((f32x4)__builtin_shufflevector(y, y, 4, 5, 6, 7), vo);
+            vo += step;
+            st16_at((f32x4)__builtin_shufflevector(y, y, 8, 9, 10, 11), vo);
+            vo += step;
+            st16_at((f32x4)__builtin_shufflevector(y, y, 12, 13, 14, 15), vo);
+            return;
+        }
         const int vo = fresh_voff() + (slot * SLOT_BYTES + t * 4096);   // + 1024 q fits the instruction's offset field
         st16_at((f32x4)__builtin_shufflevector(y, y, 0, 1, 2, 3), vo);
         st16_at((f32x4)__builtin_shufflevector(y, y, 4, 5, 6, 7), vo + 1024);
@@ -1159,16 +1237,18 @@ struct StashT {
         using f32x8 = float __attribute__((ext_vector_type(8)));
         const int off = slot * SLOT_BYTES + t * 4096;
         const int vo = load_voff();
-        const f32x4 a = __builtin_bit_cast(f32x4, ld16_at(vo, off));
-        const f32x4 b = __builtin_bit_cast(f32x4, ld16_at(vo, off + 1024));
-        const f32x4 c = __builtin_bit_cast(f32x4, ld16_at(vo, off + 2048));
-        const f32x4 d = __builtin_bit_cast(f32x4, ld16_at(vo, off + 3072));
+        const auto at = ld_offs();
+        const f32x4 a = __builtin_bit_cast(f32x4, ld16_at(vo, at(off)));
+        const f32x4 b = __builtin_bit_cast(f32x4, ld16_at(vo, at(off + 1024)));
+        const f32x4 c = __builtin_bit_cast(f32x4, ld16_at(vo, at(off + 2048)));
+        const f32x4 d = __builtin_bit_cast(f32x4, ld16_at(vo, at(off + 3072)));
         const f32x8 ab = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
         const f32x8 cd = __builtin_shufflevector(c, d, 0, 1, 2, 3, 4, 5, 6, 7);
         return __builtin_shufflevector(ab, cd, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
     }
     // MEASUREMENT BUILD ONLY (-DHN_STASH_HALF=1; not parity-preserving): the same tile as 16 fp16 values, two 16-byte accesses instead
-    // of four -- what halving the a1..a7 stash traffic of the evaluation kernel would be worth
+    // of four -- what halving the a1..a7 stash traffic of the evaluation kernel would be worth.  Not written for
+    // the packed form of a uniform wave: run such a build with HONERF_UNIFORM_STASH=0 or 2.
     __device__ __forceinline__ void tile_store_half(int slot, int t, const f32x16& y) const {
         const int vo = fresh_voff() + (slot * SLOT_BYTES + t * 4096);
         h8 a, b;
@@ -1195,14 +1275,24 @@ struct StashT {
     }
     // fragment block s (byte offset `base` + s * 2 KiB): [hi | lo][lane] 16 B
     __device__ __forceinline__ void frag_store(int base, int s, const h8& hi, const h8& lo) const {
+        if constexpr (UNI) {
+            const U u = st_offs();
+            int vo = fresh_voff() + u(base + s * KS_BYTES);
+            st16_at(hi, vo);
+            vo += u.step();
+            st16_at(lo, vo);
+            return;
+        }
         const int vo = fresh_voff() + (base + s * KS_BYTES);
         st16_at(hi, vo);
         st16_at(lo, vo + 1024);
     }
-    __device__ __forceinline__ void frag_load(int base, int s, h8& hi, h8& lo) const {
-        const int vo = load_voff();
-        const u32x4 a = ld16_at(vo, base + s * KS_BYTES);
-        const u32x4 b = ld16_at(vo, base + s * KS_BYTES + 1024);
+    // (`beyond`: wave-uniform, 0 or an offset beyond the descriptor's range -- the load then moves nothing and returns zeros)
+    __device__ __forceinline__ void frag_load(int base, int s, h8& hi, h8& lo, int beyond = 0) const {
+        const int vo = load_voff() + beyond;
+        const auto at = ld_offs();
+        const u32x4 a = ld16_at(vo, at(base + s * KS_BYTES));
+        const u32x4 b = ld16_at(vo, at(base + s * KS_BYTES + 1024));
         hi = __builtin_bit_cast(h8, a);
         lo = __builtin_bit_cast(h8, b);
     }
