@@ -184,6 +184,13 @@ SIGNATURES = {
     'hn_lpips_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong]),
     'hn_lpips': (c_i, [c_vp, c_vp, c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_sz, c_vp]),
     'hn_lpips_features': (c_i, [c_vp, c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'hn_vgg_loss_create': (c_i, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    'hn_vgg_loss_destroy': (c_i, [c_vp]),
+    'hn_vgg_loss_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong]),
+    'hn_vgg_loss_fwd': (c_i, [c_vp, c_f, c_f, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_f, c_vp, c_sz,
+                              c_vp]),
+    'hn_vgg_loss_bwd': (c_i, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_f, c_vp, c_sz, c_f,
+                              c_vp]),
 }
 
 _lib = None

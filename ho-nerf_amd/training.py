@@ -12,12 +12,15 @@ backward pass runs through `render_core` at the final depths only: here one call
   * d loss / d rays (field frame), d loss / d bt_inv, T_pose (hand).
 
 The weight-norm chain rule (d/d weight_g, d/d weight_v from d/d W; old-style `nn.utils.weight_norm`, dim 0) is one more
-call (`hn_weight_norm_bwd`, all 14 layers); what is left for the host is the optimiser (torch's Adam, as the reference).  The VGG term of exp_runner.py:213-224 stays a torch module on `color_fine` ("gated on VGG loss
-staying in torch"); it composes with this Function through autograd like any other loss on the render outputs.
+call (`hn_weight_norm_bwd`, all 14 layers); what is left for the host is the optimiser (torch's Adam, as the reference).  The VGG
+term of exp_runner.py:228-236 is `VggLoss` below (hn_vggloss.hip: VGG19's five taps, forward and backward on the device, weights
+supplied by the caller); it composes with this Function through autograd like any other loss on the render outputs
+(`vgg_extra_loss`, `train(vgg=...)`), and `patch_pixels` draws the 21 x 21 patch it needs.
 """
 import ctypes
 import math
 import os
+import sys
 
 import torch
 import torch.nn.functional as F
@@ -317,12 +320,17 @@ def allreduce_gradients(params, dist=None, average=True):
 def train_step(renderer, optimizer, rays_o, rays_d, near, far, bt_inv, T_pose_21, Ro, To, true_rgb, true_mask, igr_weight=0.1,
                mask_weight=0.1, t_rand=None, extra_loss=None, dist=None):
     """One iteration of exp_runner.train's inner loop (exp_runner.py:196-232): render, loss, backward, optimiser step.
-    `extra_loss(render_out)` adds a torch term on the render outputs (the VGG loss of :213-224).  With an initialised
+    `extra_loss(render_out)` adds a term on the render outputs (the VGG loss of :228-236: `vgg_extra_loss`); it returns a tensor, or a
+    dict whose 'loss' is added and whose other entries join the returned terms.  With an initialised
     `torch.distributed` the gradients are averaged over the ranks before the step (`allreduce_gradients`)."""
     out = render_train(renderer, rays_o, rays_d, near, far, bt_inv, T_pose_21, None, Ro, To, t_rand=t_rand)
     terms = train_loss(out, true_rgb, true_mask, igr_weight, mask_weight)
     if extra_loss is not None:
-        terms['loss'] = terms['loss'] + extra_loss(out)
+        extra = extra_loss(out)
+        if isinstance(extra, dict):        # (`vgg_extra_loss`: the weighted term under 'loss', what it logs under its own names)
+            terms.update({k: v for k, v in extra.items() if k != 'loss'})
+            extra = extra['loss']
+        terms['loss'] = terms['loss'] + extra
     optimizer.zero_grad(set_to_none=True)
     from .fitting import _unit_gradient
     terms['loss'].backward(gradient=_unit_gradient(terms['loss']))
@@ -378,7 +386,7 @@ class TrainLossFn(torch.autograd.Function):
 
 
 def train_loss(render_out, true_rgb, true_mask, igr_weight=0.1, mask_weight=0.1):
-    """The loss of exp_runner.py:202-212 without the VGG term (:213-224, a torch module on color_fine).  On the device: one launch forward
+    """The loss of exp_runner.py:202-212 without the VGG term (:228-236: `VggLoss`, added through `extra_loss`).  On the device: one launch forward
     and one backward (TrainLossFn); FUSED_TRAIN_LOSS = False / CPU tensors: the reference's statements as torch operators."""
     color_fine, weight_sum = render_out['color_fine'], render_out['weight_sum']
     if FUSED_TRAIN_LOSS and color_fine.is_cuda and color_fine.dtype == torch.float32 and color_fine.shape[0] > 0:
@@ -474,15 +482,20 @@ def latest_checkpoint(base_exp_dir):
 
 def train(renderer, batches, end_iter, base_exp_dir, learning_rate=1e-4, learning_rate_alpha=0.05, warm_up_end=5000,
           igr_weight=1.0, mask_weight=1.0, near=0.4, far=1.5, save_freq=10000, report_freq=100, is_continue=False,
-          extra_loss=None, step_fn=None, dist=None):
+          extra_loss=None, step_fn=None, dist=None, vgg=None, vgg_weight=1.0, vgg_start=None, vgg_ramp=10000):
     """The loop of exp_runner.train (exp_runner.py:126-264) without its dataset side: `batches` yields dicts with
     `rays_o, rays_d [B,3], true_rgb [B,3], true_mask [B,1]` and the frame's `bt_inv, T_pose_21` (hand) or `Ro, To`
     (object) -- what exp_runner.py:136-201 prepares per iteration.  Learning-rate schedule, checkpoints (same keys and
     names, resumable with `is_continue`) and one JSON line of metrics per `report_freq` iterations in
     `<base_exp_dir>/metrics.jsonl` (the scalars the reference sends to TensorBoard, :233-241).  `step_fn` replaces
-    `train_step` in host-only tests."""
+    `train_step` in host-only tests.  `vgg`, a `VggLoss`: the perceptual term of :134, :140-143, :228-236 -- from
+    `iter_step > vgg_start` (default 0.3 end_iter) on an iteration takes the batch's 'patch' entry where it has one (a dict of the
+    same keys: the reference's `patch_sample`) and adds `min((iter_step - vgg_start) / vgg_ramp, 1) vgg_weight VggLoss(patch)`,
+    logged as `vgg_loss`.  Without `vgg` nothing changes."""
     import json
     step_fn = step_fn or train_step
+    if vgg is not None and vgg_start is None:
+        vgg_start = 0.3 * end_iter             # exp_runner.py:134
     optimizer = make_optimizer(renderer, learning_rate)
     iter_step = 0
     if is_continue:
@@ -505,8 +518,13 @@ def train(renderer, batches, end_iter, base_exp_dir, learning_rate=1e-4, learnin
         except StopIteration:          # one epoch of the dataloader is over: start the next (exp_runner.py:133-134)
             it = iter(batches)
             b = next(it)
+        extra = extra_loss
+        if vgg is not None and iter_step > vgg_start:
+            b = b.get('patch', b)
+            if vgg_weight > 0.0:
+                extra = vgg_extra_loss(vgg, b['true_rgb'], vgg_weight, min((iter_step - vgg_start) / vgg_ramp, 1.0), also=extra_loss)
         terms = step_fn(renderer, optimizer, b['rays_o'], b['rays_d'], near, far, b.get('bt_inv'), b.get('T_pose_21'), b.get('Ro'),
-                        b.get('To'), b['true_rgb'], b['true_mask'], igr_weight, mask_weight, extra_loss=extra_loss, dist=dist)
+                        b.get('To'), b['true_rgb'], b['true_mask'], igr_weight, mask_weight, extra_loss=extra, dist=dist)
         iter_step += 1
         if iter_step % report_freq == 0:
             rec = {'iter': iter_step, 'lr': optimizer.param_groups[0]['lr']}
@@ -524,3 +542,255 @@ def train(renderer, batches, end_iter, base_exp_dir, learning_rate=1e-4, learnin
     if hasattr(renderer, 'mark_parameters_changed'):
         renderer.mark_parameters_changed()
     return iter_step
+
+
+# ---- the VGG19 perceptual loss of exp_runner.py:228-236 (utils/fields.py:407-433), hn_vggloss.hip; DESIGN.md 3.19 ------------------------
+VGG19_CONV_INDEX = (0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28)      # the Conv2d modules of torchvision's vgg19().features below 30
+VGG19_CONV_COUT = (64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512)
+VGG19_POOL_BEFORE = (2, 4, 8, 12)          # MaxPool2d(2, 2) (modules 4, 9, 18, 27) in front of these convolutions, counted from 0
+VGG19_TAP_CONVS = (0, 2, 4, 8, 12)         # feature_layers = (2, 7, 12, 21, 30): the ReLU outputs of these convolutions (relu1_1 .. relu5_1)
+VGG_MIN_SIDE = 16                          # below, the fifth tap has no pixel (torch's pool refuses it too)
+
+
+def vgg19_tensors(state, channels=VGG19_CONV_COUT):
+    """The 13 convolutions `VggLoss` takes from a state dict: (weights [Cout, Cin, 3, 3], biases [Cout]) as they lie in the dict, under
+    `features.<i>.weight | bias` (torchvision's vgg19().state_dict()) or `<i>.weight | bias` (its .features).  Every other key (the
+    convolutions 30, 32, 34, the classifier) is ignored.  `channels`: the output channels of the 13 convolutions (a narrower network
+    in the tests).  Touches no device.  ValueError names every missing or mis-shaped key."""
+    import numpy as np
+    bad, conv_w, conv_b = [], [], []
+    cin = (3,) + tuple(channels[:-1])
+    for i, ci, co in zip(VGG19_CONV_INDEX, cin, channels):
+        for leaf, shape, into in (('weight', (co, ci, 3, 3), conv_w), ('bias', (co,), conv_b)):
+            names = ('features.%d.%s' % (i, leaf), '%d.%s' % (i, leaf))
+            found = [n for n in names if n in state]
+            if not found:
+                bad.append('%s: missing' % ' | '.join(names))
+                continue
+            v = state[found[0]]
+            v = torch.from_numpy(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
+            if tuple(v.shape) != shape:
+                bad.append('%s: shape %s, expected %s' % (found[0], tuple(v.shape), shape))
+                continue
+            into.append(v)
+    if bad:
+        raise ValueError('VggLoss: ' + '; '.join(bad))
+    return conv_w, conv_b
+
+
+def patch_image(color, n0, n1):
+    """exp_runner.py:229-230: `color.reshape(n0, n1, 3).permute(2, 1, 0).unsqueeze(0)` -- image[c, y, x] = color[x n1 + y, c], height
+    n1, width n0.  With `patch_pixels`' ordering (rows vary fastest) the image is upright."""
+    return color.reshape(n0, n1, 3).permute(2, 1, 0).unsqueeze(0)
+
+
+def vgg_taps_reference(conv_w, conv_b, x, trace=None):
+    """The five taps of x [N, 3, H, W] with torch operators in x's dtype: 3x3 convolutions (stride 1, zero padding 1, bias) with ReLU,
+    MaxPool2d(2, 2) in floor mode in front of the convolutions VGG19_POOL_BEFORE, the ReLU outputs of VGG19_TAP_CONVS.  `trace`, a
+    dict: also every pre-activation under 'pre' and every pool's input under 'pool_in' (the tests look for marginal gates there)."""
+    taps = []
+    for l, (w, b) in enumerate(zip(conv_w, conv_b)):
+        if l in VGG19_POOL_BEFORE:
+            if trace is not None:
+                trace.setdefault('pool_in', []).append(x)
+            x = F.max_pool2d(x, 2, 2)
+        pre = F.conv2d(x, w.detach().to(x), b.detach().to(x), stride=1, padding=1)
+        if trace is not None:
+            trace.setdefault('pre', []).append(pre)
+        x = F.relu(pre)
+        if l in VGG19_TAP_CONVS:
+            taps.append(x)
+    return taps
+
+
+def vgg_loss_reference(conv_w, conv_b, source, target):
+    """VGGLoss.forward (utils/fields.py:424-433) restated with torch operators in `source`'s dtype: source, target [1, 3, H, W] as they
+    are (no normalisation) -> (loss, [the five L1 means]).  The target runs under no_grad; the weights carry no gradient.  The
+    yardstick of the device path, and what `VggLoss` runs on CPU tensors or another dtype than float32."""
+    ts = vgg_taps_reference(conv_w, conv_b, source)
+    with torch.no_grad():
+        tt = vgg_taps_reference(conv_w, conv_b, target.detach().to(source))
+    means = [F.l1_loss(a, b) for a, b in zip(ts, tt)]
+    loss = means[0]
+    for m in means[1:]:
+        loss = loss + m
+    return loss, means
+
+
+class VggLossFn(torch.autograd.Function):
+    """(source, target: contiguous fp32 device buffers read as [y sy + x sx + c sc]) -> (loss [], terms [6] = loss, the five tap means --
+    not differentiable).  hn_vgg_loss_fwd; the backward pass is hn_vgg_loss_bwd on the workspace the forward call filled, and gives
+    d loss / d source alone."""
+
+    @staticmethod
+    def forward(ctx, vgg, source, target, h, w, sy, sx, sc):
+        L = _lib
+        lib = L.load()
+        handle = vgg._model(source.device)
+        with torch.cuda.device(source.device):
+            need = int(lib.hn_vgg_loss_workspace_bytes(h, w))
+            if need == 0:
+                raise ValueError('VggLoss: %s' % (lib.hn_last_error() or b'').decode())
+            ws = torch.empty(need, dtype=torch.uint8, device=source.device)     # this call's own: the backward pass reads it
+            terms = torch.empty(6, dtype=torch.float32, device=source.device)
+            L.check(lib.hn_vgg_loss_fwd(handle, L.ptr(source), L.ptr(target), h, w, sy, sx, sc, L.ptr(terms), L.ptr(ws), need, L.stream_ptr()), 'hn_vgg_loss_fwd')
+        ctx.vgg, ctx.ws, ctx.geom, ctx.like = vgg, ws, (h, w, sy, sx, sc), (tuple(source.shape), source.device)    # (not the tensor: nothing of it is read again)
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)
+        return terms[0], terms
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable      # (a second derivative is not offered: asking for one raises instead of treating g as a constant)
+    def backward(ctx, g_loss, _g_terms):
+        if g_loss is None:
+            return (None,) * 8
+        L = _lib
+        lib = L.load()
+        h, w, sy, sx, sc = ctx.geom
+        shape, dev = ctx.like
+        with torch.cuda.device(dev):
+            g = torch.empty(shape, dtype=torch.float32, device=dev)
+            gl = L.f32(g_loss, dev).reshape(1)
+            L.check(lib.hn_vgg_loss_bwd(ctx.vgg._model(dev), h, w, sy, sx, sc, L.ptr(gl), L.ptr(ctx.ws), ctx.ws.numel(), L.ptr(g), L.stream_ptr()), 'hn_vgg_loss_bwd')
+        return None, g, None, None, None, None, None, None
+
+
+class VggLoss:
+    """utils/fields.py:407-433 `VGGLoss` with its defaults (five taps relu1_1 .. relu5_1 of VGG19, weights 1, nn.L1Loss means, the
+    input as it is), forward and backward on the device (hn_vggloss.hip), differentiable with respect to the source only.
+
+    `state` maps names to tensors (or numpy arrays) and holds the first 13 convolutions of VGG19's `features` under
+      features.<i>.weight | bias        torchvision's vgg19().state_dict()
+      <i>.weight | bias                 vgg19().features.state_dict()
+    (i = 0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28); every other key is ignored, a missing key or a wrong shape raises ValueError
+    naming every offending key.  Nothing is downloaded: the pretrained weights are a file of torchvision's.  The layouts are stated
+    from that package's public format; the tests build such dicts themselves.
+
+    float32 CUDA tensors take the device path (the packed model is made on the first such call, on that tensor's device); CPU tensors
+    and other dtypes take `vgg_loss_reference`.  `last_terms`: the five tap means of the last call (a detached tensor [5])."""
+
+    def __init__(self, state):
+        self.conv_weight, self.conv_bias = vgg19_tensors(state)
+        self._handle, self._device, self._keep = None, None, None
+        self.last_terms = None
+
+    @classmethod
+    def load(cls, path):
+        """From a file written with torch.save that holds a state dict of one of the layouts above."""
+        state = torch.load(path, map_location='cpu')
+        if not isinstance(state, dict):
+            raise ValueError('VggLoss.load: the file holds a %s, expected a state dict' % type(state).__name__)
+        return cls(state)
+
+    def _model(self, device):
+        if self._handle is None:
+            with torch.cuda.device(device):
+                w = [_lib.f32(x, device) for x in self.conv_weight]
+                b = [_lib.f32(x, device) for x in self.conv_bias]
+                arr = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+                handle = ctypes.c_void_p()
+                _lib.check(_lib.load().hn_vgg_loss_create(arr(w), arr(b), ctypes.byref(handle), _lib.stream_ptr()), 'hn_vgg_loss_create')
+            self._handle, self._device = handle, torch.device(device)
+        elif torch.device(device) != self._device:
+            raise ValueError('VggLoss: the model is on %s, the images are on %s' % (self._device, device))
+        return self._handle
+
+    def __del__(self):
+        handle, self._handle = getattr(self, '_handle', None), None
+        if handle is not None and not sys.is_finalizing():       # at interpreter exit the driver takes the allocation back
+            try:
+                _lib.load().hn_vgg_loss_destroy(handle)
+            except Exception:
+                pass
+
+    @staticmethod
+    def _on_device(source, target):
+        return source.is_cuda and source.dtype == torch.float32 and target.dtype == torch.float32
+
+    def _finish(self, loss, means):
+        self.last_terms = means.detach() if isinstance(means, torch.Tensor) else torch.stack([m.detach() for m in means])
+        return loss
+
+    def forward(self, source, target):
+        """VGGLoss.forward(source, target) on [1, 3, H, W] (H, W >= 16) -> the loss, a 0-d tensor."""
+        if source.dim() != 4 or source.shape[0] != 1 or source.shape[1] != 3 or tuple(target.shape) != tuple(source.shape):
+            raise ValueError('VggLoss: source %s, target %s: expected two [1, 3, H, W]' % (tuple(source.shape), tuple(target.shape)))
+        H, W = int(source.shape[2]), int(source.shape[3])
+        if min(H, W) < VGG_MIN_SIDE:
+            raise ValueError('VggLoss: images of %d x %d, at least 16 x 16 (the fifth tap is floor(H / 16) x floor(W / 16))' % (H, W))
+        if not self._on_device(source, target):
+            return self._finish(*vgg_loss_reference(self.conv_weight, self.conv_bias, source, target))
+        loss, terms = VggLossFn.apply(self, source.contiguous(), target.detach().to(source.device).contiguous(), H, W, W, 1, H * W)
+        return self._finish(loss, terms[1:])
+
+    __call__ = forward
+
+    def patch_loss(self, color_fine, true_rgb, n0=None, n1=None):
+        """exp_runner.py:229-234 on the render output of a patch: color_fine, true_rgb [P, 3] in the layout of `patch_image` (P = n0 n1;
+        default n0 = n1 = isqrt(P), the reference's H_prime) -> the loss.  The device path reads the two buffers through strides: the
+        reference's reshape / permute costs no copy."""
+        P = int(color_fine.shape[0])
+        if tuple(color_fine.shape) != (P, 3) or tuple(true_rgb.shape) != (P, 3):
+            raise ValueError('VggLoss.patch_loss: color_fine %s, true_rgb %s: expected two [P, 3]' % (tuple(color_fine.shape), tuple(true_rgb.shape)))
+        if n0 is None and n1 is None:
+            n0 = n1 = math.isqrt(P)
+            if n0 * n1 != P:
+                raise ValueError('VggLoss.patch_loss: %d rays are no square patch: pass n0 and n1' % P)
+        elif n0 is None or n1 is None or int(n0) * int(n1) != P:
+            raise ValueError('VggLoss.patch_loss: n0 = %s, n1 = %s for %d rays' % (n0, n1, P))
+        n0, n1 = int(n0), int(n1)
+        if min(n0, n1) < VGG_MIN_SIDE:
+            raise ValueError('VggLoss: images of %d x %d, at least 16 x 16 (the fifth tap is floor(H / 16) x floor(W / 16))' % (n1, n0))
+        if not self._on_device(color_fine, true_rgb):
+            return self._finish(*vgg_loss_reference(self.conv_weight, self.conv_bias, patch_image(color_fine, n0, n1), patch_image(true_rgb, n0, n1)))
+        loss, terms = VggLossFn.apply(self, color_fine.contiguous(), true_rgb.detach().to(color_fine.device).contiguous(), n1, n0, 3, 3 * n1, 1)
+        return self._finish(loss, terms[1:])
+
+
+def vgg_extra_loss(vgg, true_rgb, weight=1.0, rate=1.0, n0=None, n1=None, also=None):
+    """The `extra_loss` of `train_step` for exp_runner.py:228-236: render_out -> dict(loss = rate weight VggLoss(color_fine, true_rgb)
+    (+ also(render_out)), vgg_loss = the unweighted value, detached -- what the reference logs).  `rate`: its cur_iter_rate."""
+    def extra(render_out):
+        v = vgg.patch_loss(render_out['color_fine'], true_rgb, n0, n1)
+        loss = (float(rate) * float(weight)) * v
+        out = dict(vgg_loss=v.detach())
+        if also is not None:
+            more = also(render_out)
+            if isinstance(more, dict):
+                out.update({k: x for k, x in more.items() if k != 'loss'})
+                more = more['loss']
+            loss = loss + more
+        out['loss'] = loss
+        return out
+    extra.vgg, extra.weight, extra.rate = vgg, float(weight), float(rate)
+    return extra
+
+
+def patch_pixels(mask, n_rays, rng):
+    """get_rays_xy_mask (utils/dataset.py:52-78) with integers: one c x c patch, c = isqrt(n_rays), near the mask [H, W] ->
+    (rays_xy [c c, 2] float32, rows [c c], cols [c c], flat = rows W + cols).  Along each axis the patch's exclusive end is drawn
+    uniformly from [min(lo + c, hi), max(lo + c, hi)] with lo, hi the mask's smallest and largest index on that axis (:55-66).  Flat
+    order is that of meshgrid(rows, cols, indexing='xy') (:69-71): ray p is row r0 + p % c, column c0 + p // c -- rows vary fastest, so
+    that `patch_image` of the gathered colours is the image crop, upright.  NDC as in `fitting.mask_pixels`:
+    x = -(col - W / 2) / (H / 2), y = -(row - H / 2) / (H / 2) (:74-77).  `rng`: a numpy Generator (the geometry is the reference's, the
+    draw is not: it uses Python's `random`).  Where the reference's window would leave the image -- a mask shorter than c next to a
+    border: there it wraps a negative index or raises -- the window is shifted inside."""
+    import numpy as np
+    H, W = mask.shape
+    c = math.isqrt(int(n_rays))
+    if c < 1 or c > H or c > W:
+        raise ValueError('patch_pixels: a %d x %d patch does not fit a %d x %d image' % (c, c, H, W))
+    rr, cc = np.nonzero(np.asarray(mask) > 0)
+    if len(rr) == 0:
+        raise ValueError('patch_pixels: the mask is empty')
+
+    def start(lo, hi, size):
+        end = int(rng.integers(min(lo + c, hi), max(lo + c, hi) + 1))
+        return min(max(end - c, 0), size - c)
+
+    r0, c0 = start(int(rr.min()), int(rr.max()), H), start(int(cc.min()), int(cc.max()), W)
+    p = np.arange(c * c)
+    rows, cols = r0 + p % c, c0 + p // c
+    x = -(cols - W / 2.0) / (H / 2.0)
+    y = -(rows - H / 2.0) / (H / 2.0)
+    return np.stack([x, y], -1).astype(np.float32), rows, cols, rows * W + cols

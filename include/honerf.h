@@ -771,6 +771,34 @@ int hn_lpips(const hn_lpips_model* model, const unsigned char* a, const unsigned
 int hn_lpips_features(const hn_lpips_model* model, const unsigned char* img, long long n_images, long long height, long long width, float* tap0,
                       float* tap1, float* tap2, float* tap3, float* tap4, void* workspace, size_t workspace_bytes, hn_stream_t stream);
 
+/* ---- the VGG19 perceptual loss of training (hn_vggloss.hip): utils/fields.py:407-433, exp_runner.py:228-236 on the device -------------
+ * loss = sum_k mean |tap_k(source) - tap_k(target)| over the ReLU outputs of the convolutions 0, 2, 4, 8, 12 (counted from 0) of VGG19's
+ * `features` (module indices 0, 5, 10, 19, 28 of the 13 3x3 convolutions at 0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28;
+ * MaxPool2d(2, 2), floor mode, at 4, 9, 18, 27; 64, 128, 256, 512, 512 channels, floor(H / 2^k) x floor(W / 2^k)), all weights 1, the
+ * input as it is (no normalisation), and its gradient with respect to `source` alone under torch's conventions (sign(0) = 0, ReLU
+ * passes where its output is > 0, the pool sends to the first maximum of a window in row-major order).  One image pair per call.
+ * source, target, g_source: fp32 buffers addressed as [y stride_y + x stride_x + c stride_c] (elements; positive), y < height,
+ * x < width, c < 3: torch's [1, 3, H, W] is (W, 1, H W), the render output color_fine [P, 3] in the reference's
+ * reshape(n0, n1, 3).permute(2, 1, 0) is height = n1, width = n0, (3, 3 n1, 1).  Exact-fp32 MFMA; neither call synchronises or
+ * allocates, every sum runs in an order the shape alone decides, no floating-point atomics: the same bits on every run.  height and
+ * width >= 16, 2 x H x W x 64 below 2^31; a refused size, a NULL pointer or a short workspace is HN_EINVAL with a message, before
+ * anything is launched.
+ *   hn_vgg_loss_create: conv_weight, conv_bias: HOST arrays of 13 device pointers, fp32 [Cout, Cin, 3, 3] and [Cout] in torch's layout.
+ *     Packs the weights for both directions into one device allocation (hipMalloc) and synchronises the stream.
+ *   hn_vgg_loss_destroy: hipFree (waits for the device); NULL is fine.
+ *   hn_vgg_loss_workspace_bytes: the workspace of one forward / backward pair (0 for sizes it refuses);
+ *   hn_vgg_loss_fwd: terms [6] fp32 = the loss, then the five tap means; leaves every layer's output in the workspace;
+ *   hn_vgg_loss_bwd: g_source = g_loss (a device scalar) x d loss / d source, from the workspace the forward call of the same size
+ *     filled. */
+typedef struct hn_vgg_loss_model hn_vgg_loss_model;  /* opaque: the packed weights of the 13 convolutions, both directions */
+int hn_vgg_loss_create(const float* const* conv_weight, const float* const* conv_bias, hn_vgg_loss_model** out, hn_stream_t stream);
+int hn_vgg_loss_destroy(hn_vgg_loss_model* model);
+size_t hn_vgg_loss_workspace_bytes(long long height, long long width);
+int hn_vgg_loss_fwd(const hn_vgg_loss_model* model, const float* source, const float* target, long long height, long long width, long long stride_y,
+                    long long stride_x, long long stride_c, float* terms, void* workspace, size_t workspace_bytes, hn_stream_t stream);
+int hn_vgg_loss_bwd(const hn_vgg_loss_model* model, long long height, long long width, long long stride_y, long long stride_x, long long stride_c,
+                    const float* g_loss, void* workspace, size_t workspace_bytes, float* g_source, hn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
