@@ -701,6 +701,12 @@ int uniform_stash_mode() {
     if (e == nullptr) return 1;
     return e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1);
 }
+// HONERF_FAR_TILES, read per hand-field launch (hn_field2_hand.hip, Hand2Args::far_tiles): unset or 1 = a sample tile whose four waves
+// are all far runs the all-far tile program of the full evaluation kernels; 0 = every tile runs the general program (the same bits)
+int far_tiles_mode() {
+    const char* e = getenv("HONERF_FAR_TILES");
+    return (e != nullptr && e[0] == '0') ? 0 : 1;
+}
 
 // bump allocator over the caller's workspace
 struct Arena {

@@ -56,6 +56,8 @@ int quad_max_blocks_override();   // hn_debug_quad_max_blocks: -1 = default sele
 int uniform_stash_mode();         // hn_api.hip: HONERF_UNIFORM_STASH, read per launch (Hand2Args::ustash): 0 = every wave of the hand evaluation
                                   // kernel moves its stash at full width; 2 = a wave whose samples are all far keeps one column, in
                                   // place; unset or 1 = that column packed into whole cache lines
+int far_tiles_mode();             // hn_api.hip: HONERF_FAR_TILES, read per launch (Hand2Args::far_tiles): 0 = every tile of the hand evaluation
+                                  // kernel runs the general tile program; unset or 1 = all-far tiles run their own
 int pace_phantom_members();    // hn_debug_pace_phantom: members that never arrive at the XCD meetings (timeout-path test hook), 0 = off
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): `mask` is the kernel's own
 // bit set of devices already configured (a static std::atomic<uint64_t> next to the launch).

@@ -32,6 +32,13 @@
 #ifndef HN_EXP_ACC
 #define HN_EXP_ACC 4
 #endif
+#ifndef HN_FAR_TILES   // 1: the full evaluation kernels carry the all-far tile program (FarStash below); 0: the general program alone
+#if (defined(HN_STASH_HALF) && HN_STASH_HALF) || (defined(HN_DBG_NO_FEAT_LOADS) && HN_DBG_NO_FEAT_LOADS)
+#define HN_FAR_TILES 0   // (the measurement builds are builds of the general program)
+#else
+#define HN_FAR_TILES 1
+#endif
+#endif
 #ifndef HN_DEFER_STASH
 #define HN_DEFER_STASH 0   // 1: the fp32 activation tiles of the hidden layers go to the stash one chunk late (to_regs_hold): measured, no gain
 #endif
@@ -68,6 +75,8 @@ struct Hand2Args {
     int ustash; // HONERF_UNIFORM_STASH (hn_api.hip: uniform_stash_mode), the full evaluation (MODE 1) only: a wave whose samples are all far
                 // moves one column of its stash per half instead of 32.  Holds StashT::umask of such a wave, USTASH_COLS, plus -- packed
                 // form -- StashT::ush in its low four bits (USTASH_SHIFT); 0 = off
+    int far_tiles;   // HONERF_FAR_TILES (hn_api.hip: far_tiles_mode) and the packed uniform stash, the full evaluation (MODE 1) only: a tile
+                     // whose four waves are all far runs the all-far tile program (FarStash below); 0 = every tile runs the general one
     // adjoint (MODE 2): upstream gradients in, input / pose gradients out
     const float* g_sdf;    // [n]
     const float* g_grad;   // [n,3]
@@ -142,6 +151,69 @@ constexpr int POSE_ROW = 256;                // floats per wave and frame: 21 bo
 constexpr int POSE_FRAMES = 2;               // frames a WAVE may touch for the atomics-free pose gradients: its first sample's and the next
 constexpr int POSE_MAX_TILES = 8192;         // tiles of a launch up to which the rows are kept (8 KiB per tile); beyond: atomics
 constexpr size_t HAND2_LDS_POSE = 2 * CHUNK_MAX + WG_WAVES * STAGE_BYTES + 16;   // (+ 16: the 4 per-wave bone masks of the culling)
+
+// ---- the all-far tile program's stash (MODE 1 on the 32x32x16 shape) ----------------------------------------------------------------
+// A sample tile whose FOUR waves have nz == 0 is run by a second instance of the tile program (field2_hand_body: `program`) in which
+// that is a compile-time fact: no feature fragments are generated, stored or loaded (load_bone is zero registers), the leftover block
+// and the Jacobian pass's staging and contractions are gone (their MFMAs run: dense compute), and what the general program parks in
+// the wave's packed global image -- the sites a1..a7, HS_DZ7, HS_FVEC, HS_DZ4 of USTASH_SITES; the leftover feature blocks are zeros
+// and are not kept -- lives in LDS: 32 bytes [half 0 | half 1] per 1 KiB instruction block of the slots 0 .. HS_DZ4, the packed image's
+// own map (ustash_packed) from region 0, 10 KiB per wave behind the kernel's other LDS.  The lanes with j == 0 store there; the other
+// lanes' stores go to the wave's staging area (idle in this program), 16 bytes per lane, so that no store needs a branch or an EXEC
+// change inside the MFMA stream; every lane reads the 16 bytes of its half (a broadcast read).
+constexpr int FAR_IMAGE_BYTES = (HS_DZ4 + 1) * (SLOT_BYTES >> USTASH_SHIFT);
+static_assert(HS_A1 == 0 && HS_DZ7 == 7 && HS_FVEC == 8 && HS_DZ4 == 9 && FAR_IMAGE_BYTES == 10240 && HAND2_LDS_POSE % 16 == 0 && STAGE_BYTES >= 1024,
+              "the all-far image covers the slots 0 .. HS_DZ4 and its stores' dump is the wave's staging area");
+constexpr size_t HAND2_LDS_EVAL = HAND2_LDS_POSE + WG_WAVES * FAR_IMAGE_BYTES;   // the full evaluation kernels' LDS (they keep no pose rows)
+static_assert(HAND2_LDS_EVAL <= 160 * 1024, "LDS of a CU");
+struct FarStash {
+    char* img;    // this wave's image
+    char* dump;   // 1 KiB that nobody reads
+    __device__ __forceinline__ void init(char* lds, int wave) {
+        img = lds + HAND2_LDS_POSE + wave * FAR_IMAGE_BYTES;
+        dump = lds + 2 * CHUNK_MAX + wave * STAGE_BYTES;
+    }
+    // where this lane stores its 16 bytes of the block at byte offset `off` (a multiple of 1 KiB) of the wave's region
+    __device__ __forceinline__ char* st_at(int off) const {
+        const int l16 = lane_x16();
+        return (l16 & USTASH_COLS) != 0 ? dump + l16 : img + ustash_packed(0, off, 0) + (l16 >> USTASH_SHIFT);
+    }
+    __device__ __forceinline__ const char* ld_at(int off) const { return img + ustash_packed(0, off, 0) + ((lane_x16() & 512) >> USTASH_SHIFT); }
+    __device__ __forceinline__ void tile_store(int slot, int t, const f32x16& y) const {
+        using f32x4 = float __attribute__((ext_vector_type(4)));
+        const int off = slot * SLOT_BYTES + t * 4096;
+        char* const p = st_at(off);   // (the four blocks of a tile are 32 bytes apart in both destinations' strides: the dump gets 16 + 3 * 32)
+        const int step = 1024 >> USTASH_SHIFT;
+        *reinterpret_cast<f32x4*>(p) = __builtin_shufflevector(y, y, 0, 1, 2, 3);
+        *reinterpret_cast<f32x4*>(p + step) = __builtin_shufflevector(y, y, 4, 5, 6, 7);
+        *reinterpret_cast<f32x4*>(p + 2 * step) = __builtin_shufflevector(y, y, 8, 9, 10, 11);
+        *reinterpret_cast<f32x4*>(p + 3 * step) = __builtin_shufflevector(y, y, 12, 13, 14, 15);
+    }
+    __device__ __forceinline__ f32x16 tile_load(int slot, int t) const {
+        using f32x4 = float __attribute__((ext_vector_type(4)));
+        using f32x8 = float __attribute__((ext_vector_type(8)));
+        const int off = slot * SLOT_BYTES + t * 4096;
+        const char* const p = ld_at(off);
+        const int step = 1024 >> USTASH_SHIFT;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(p);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(p + step);
+        const f32x4 c = *reinterpret_cast<const f32x4*>(p + 2 * step);
+        const f32x4 d = *reinterpret_cast<const f32x4*>(p + 3 * step);
+        const f32x8 ab = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+        const f32x8 cd = __builtin_shufflevector(c, d, 0, 1, 2, 3, 4, 5, 6, 7);
+        return __builtin_shufflevector(ab, cd, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+    }
+    __device__ __forceinline__ void frag_store(int base, int s, const h8& hi, const h8& lo) const {
+        char* const p = st_at(base + s * KS_BYTES);
+        *reinterpret_cast<h8*>(p) = hi;
+        *reinterpret_cast<h8*>(p + (1024 >> USTASH_SHIFT)) = lo;
+    }
+    __device__ __forceinline__ void frag_load(int base, int s, h8& hi, h8& lo) const {
+        const char* const p = ld_at(base + s * KS_BYTES);
+        hi = *reinterpret_cast<const h8*>(p);
+        lo = *reinterpret_cast<const h8*>(p + (1024 >> USTASH_SHIFT));
+    }
+};
 
 constexpr int HB_HID = chunk_bytes(1, 16, true);
 constexpr int HB_BWD = chunk_bytes(1, 16, false);
@@ -442,8 +514,11 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
     // instead of 640 lines touched for as much.  A wave with any live lane, the sdf-only kernel and every taped / adjoint mode (their
     // tape is read by other launches) move the stash at full width.
     constexpr bool USTASH = MODE == 1 && !S16;
-    StashT<(MODE <= 1 || (HN_ADJ_WB && MODE >= 4)) ? STASH_ST_AUX : STASH_AUX, USTASH> sh;   // (evaluation kernels: write-back stores; taped / adjoint kernels: nt -- hn_mlp2.h)
-    sh.init(a.scratch + ((size_t)blockIdx.x * WG_WAVES + wave) * N_SLOTS * SLOT_F4, N_SLOTS, lane);
+    StashT<(MODE <= 1 || (HN_ADJ_WB && MODE >= 4)) ? STASH_ST_AUX : STASH_AUX, USTASH> shg;   // (evaluation kernels: write-back stores; taped / adjoint kernels: nt -- hn_mlp2.h)
+    shg.init(a.scratch + ((size_t)blockIdx.x * WG_WAVES + wave) * N_SLOTS * SLOT_F4, N_SLOTS, lane);
+    constexpr bool FAR_ARM = USTASH && HN_FAR_TILES;   // the kernel carries the all-far tile program
+    [[maybe_unused]] FarStash shf;
+    if constexpr (FAR_ARM) shf.init(lds, wave);
     constexpr int FEAT = HS_FEAT * SLOT_BYTES;   // byte offset of the feature fragment blocks
     constexpr int LEFT = HS_LEFT * SLOT_BYTES;   // ... of the leftover values
     constexpr int GXB = HS_GXB * SLOT_BYTES;     // adjoint: J gb, same block layout as the features ...
@@ -502,26 +577,26 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 bone_to_p<false>(Sv, Sr, bn, M + 16 * b, g);
         };
 
-        if constexpr (PER_TILE) sh.init(a.scratch + ((size_t)tile * WG_WAVES + wave) * N_SLOTS * SLOT_F4, N_SLOTS, lane);
+        if constexpr (PER_TILE) shg.init(a.scratch + ((size_t)tile * WG_WAVES + wave) * N_SLOTS * SLOT_F4, N_SLOTS, lane);
         // ---- F0: features of the 21 bones -> fragments in the stash -------------------------------------
         // nz bit b: some sample of this wave has a non-zero mask h for bone b.  Where none has, all 64
         // features of the bone are exactly 0 for the whole wave: nothing is generated or stored, and the
         // consumers substitute zero fragments instead of loading (the MFMAs still run: dense compute).
         ws.stamp(7);   // (points and frame known)
-        unsigned nz = 0;
+        unsigned nz_w = 0;
         if constexpr (USTASH) {   // (the live bones' fragments below are stored before the wave knows what it is)
-            sh.umask = 0;
-            sh.set_packed(0, 0);
+            shg.umask = 0;
+            shg.set_packed(0, 0);
         }
         if constexpr (!RUN_FWD) {
-            nz = __builtin_bit_cast(unsigned, sh.f32_load(NZ_OFF));   // as the evaluation launch left it
+            nz_w = __builtin_bit_cast(unsigned, shg.f32_load(NZ_OFF));   // as the evaluation launch left it
         } else {
 #pragma unroll 1
         for (int b = 0; b < N_BONES; ++b) {
             const Bone2 bn = coords(b);
             const bool any = __ballot(bn.hh != 0.f) != 0ull;
             if (any) {
-                nz |= 1u << b;
+                nz_w |= 1u << b;
                 float f[4][8];
                 bone_features2(bn, h, f);
                 h8 fh[4], fl[4];
@@ -533,13 +608,49 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     frags_in(fl[s], fl[s + 1]);
                 }
 #pragma unroll
-                for (int s = 0; s < 4; ++s) sh.frag_store(FEAT, 4 * b + s, fh[s], fl[s]);
+                for (int s = 0; s < 4; ++s) shg.frag_store(FEAT, 4 * b + s, fh[s], fl[s]);
+                // (a kernel with the all-far program: the leftover value of a bone that is not live, +0, is stored behind the loop, in the
+                //  general program, by the waves that read it back; an all-far tile stores nothing here)
+                if constexpr (FAR_ARM) shg.f32_store(LEFT + b * 256, (h ? bn.r[2] : bn.r[1]) * bn.hh);
             }
-            sh.f32_store(LEFT + b * 256, any ? (h ? bn.r[2] : bn.r[1]) * bn.hh : 0.f);
+            if constexpr (!FAR_ARM) shg.f32_store(LEFT + b * 256, any ? (h ? bn.r[2] : bn.r[1]) * bn.hh : 0.f);
         }
-        nz = __builtin_amdgcn_readfirstlane(nz);
-        // from here to the end of the tile a uniform wave moves one stash column per half (the 21 leftover values above are stored at full
-        // width: the wave is not known to be uniform before its last bone; they are all +0 and are not read back)
+        nz_w = __builtin_amdgcn_readfirstlane(nz_w);
+        }   // RUN_FWD
+        nz_w = __builtin_amdgcn_readfirstlane(nz_w);
+
+        // nzw: the bones whose weight chunks this workgroup runs.  Dense: all of them.  Culled: those that are live
+        // in at least one of the 4 waves (the chunks are shared through LDS, so the skip has to be workgroup-wide),
+        // plus bone 0, whose first chunk is always in flight when a pass starts.
+        // far (a kernel with the all-far program): no wave of this tile has a live bone, by the kernel's own masks, in a dense launch
+        // that asked for it -- the workgroup runs the tile with the all-far program.  One choice per tile, workgroup-uniform: both
+        // programs pass the same barriers and consume the same weight stream, chunk for chunk.
+        // (A kernel without that program exchanges the masks where it always did, behind the leftover block and for a culled launch alone.)
+        unsigned nzw_w = (1u << N_BONES) - 1u;
+        bool far = false;
+        if constexpr (FAR_ARM) {
+            unsigned* ex = reinterpret_cast<unsigned*>(lds + 2 * CHUNK_MAX + WG_WAVES * STAGE_BYTES);
+            if (lane == 0) ex[wave] = nz_w;
+            __syncthreads();
+            const unsigned nz_any = __builtin_amdgcn_readfirstlane(ex[0] | ex[1] | ex[2] | ex[3]);
+            if (a.cull) nzw_w = nz_any | 1u;
+            far = nz_any == 0u && a.cull == 0 && a.far_tiles != 0;
+        }
+        // the tile program from here on: FAR_ = the all-far instance (returns true where a phase-timing build leaves the kernel)
+        auto program = [&](auto FAR_) __attribute__((always_inline)) -> bool {
+        constexpr bool FAR = decltype(FAR_)::value;
+        const unsigned nz = FAR ? 0u : nz_w;
+        unsigned nzw = FAR ? (1u << N_BONES) - 1u : nzw_w;
+        auto& sh = [&]() -> auto& {
+            if constexpr (FAR)
+                return shf;
+            else
+                return shg;
+        }();
+        if constexpr (RUN_FWD && !FAR) {
+        // from here to the end of the tile a uniform wave moves one stash column per half (a kernel without the all-far program has stored
+        // the 21 leftover values above at full width: the wave is not known to be uniform before its last bone; they are all +0 and are
+        // not read back)
         // (the mask value comes from the host: formed here from a flag, the flag's test is hoisted out of the tile loop as a lane mask, and
         //  the first feature pass's load_bone(0) ends up with waits in its zero arm -- tests/test_abi.py's static check of the ISA)
         //  -- and so do the shift and the region of the packed form, by arithmetic on that value)
@@ -547,6 +658,13 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             const int us = nz == 0u ? a.ustash : 0;
             sh.umask = us & USTASH_COLS;
             sh.set_packed(us & 15, (us & 15) << 16);
+            if constexpr (FAR_ARM) {
+                if (us == 0) {   // this wave reads its 21 leftover values back: +0 for the bones that are not live
+#pragma unroll 1
+                    for (int b = 0; b < N_BONES; ++b)
+                        if (!((nz >> b) & 1u)) sh.f32_store(LEFT + b * 256, 0.f);
+                }
+            }
         }
         ws.stamp(8);   // (bone loop of the feature generation done)
         {   // leftover block: element j of k-step u belongs to bone 8u + j
@@ -567,20 +685,16 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             for (int u = 0; u < KS_LEFT; ++u) sh.frag_store(FEAT, FEAT_BLOCKS + u, fh[u], fl[u]);
         }
         if constexpr (ADJ) sh.f32_store(NZ_OFF, __builtin_bit_cast(float, nz));
-        }   // RUN_FWD
-        nz = __builtin_amdgcn_readfirstlane(nz);
-
-        // nzw: the bones whose weight chunks this workgroup runs.  Dense: all of them.  Culled: those that are live
-        // in at least one of the 4 waves (the chunks are shared through LDS, so the skip has to be workgroup-wide),
-        // plus bone 0, whose first chunk is always in flight when a pass starts.
-        unsigned nzw = (1u << N_BONES) - 1u;
-        if (a.cull) {
-            unsigned* ex = reinterpret_cast<unsigned*>(lds + 2 * CHUNK_MAX + WG_WAVES * STAGE_BYTES);
-            if (lane == 0) ex[wave] = nz;
-            __syncthreads();
-            nzw = __builtin_amdgcn_readfirstlane(ex[0] | ex[1] | ex[2] | ex[3] | 1u);
+        }   // the general program's leftover block
+        if constexpr (!FAR_ARM) {
+            if (a.cull) {
+                unsigned* ex = reinterpret_cast<unsigned*>(lds + 2 * CHUNK_MAX + WG_WAVES * STAGE_BYTES);
+                if (lane == 0) ex[wave] = nz;
+                __syncthreads();
+                nzw = __builtin_amdgcn_readfirstlane(ex[0] | ex[1] | ex[2] | ex[3] | 1u);
+            }
         }
-        if ((HN_DBG(a) >> 8) == 1) return;   // phase timing aid
+        if ((HN_DBG(a) >> 8) == 1) return true;   // phase timing aid
         ws.stamp(9);   // (feature generation done)
         h8 ah[16], al[16], bh[16], bl[16];   // ping-pong activation fragments
         struct Act {
@@ -673,9 +787,9 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
 #define HN_DBG_NO_FEAT_LOADS 0   // 1 (measurement only, WRONG results): the feature passes never read the bones' fragments back from the stash -- an
                                  // upper bound on what reading them twice instead of four times could buy (round 5, profiles/r05/README.md)
 #endif
-        auto bone_loads = [&](int b) { return !HN_DBG_NO_FEAT_LOADS && (USTASH || b >= N_BONES || ((nz >> b) & 1u)); };   // load_bone issues its 8 loads
+        auto bone_loads = [&](int b) { return !FAR && !HN_DBG_NO_FEAT_LOADS && (USTASH || b >= N_BONES || ((nz >> b) & 1u)); };   // load_bone issues its 8 loads
         auto load_bone = [&](int b, h8(&oh)[4], h8(&ol)[4]) {
-            if constexpr (USTASH) {
+            if constexpr (USTASH && !FAR) {
                 // No branch here: the fragments of a bone that is not live are LOADED from beyond the descriptor's range, which moves
                 // nothing and returns zeros (as f32_load_z).  As the two arms of a branch, the zero arm of the first feature pass's
                 // load_bone(0) comes out behind the loads with waits for them in front of its moves (tests/test_abi.py's static check
@@ -684,9 +798,24 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 const int beyond = (int)((live ^ 1u) << 30);
 #pragma unroll
                 for (int s = 0; s < 4; ++s) sh.frag_load(feat_base, 4 * b + s, oh[s], ol[s], beyond);
-            } else if (!HN_DBG_NO_FEAT_LOADS && (b >= N_BONES || ((nz >> b) & 1u))) {
+            } else if (!FAR && !HN_DBG_NO_FEAT_LOADS && (b >= N_BONES || ((nz >> b) & 1u))) {
+                if constexpr (!FAR) {
 #pragma unroll
-                for (int s = 0; s < 4; ++s) sh.frag_load(feat_base, 4 * b + s, oh[s], ol[s]);
+                    for (int s = 0; s < 4; ++s) sh.frag_load(feat_base, 4 * b + s, oh[s], ol[s]);
+                }
+            } else if constexpr (FAR) {
+                // the all-far program: every bone and the leftover block, zero registers and no loads.  One zero fragment that the compiler
+                // has to treat as a run-time value: with literal zeros as the feature passes' B operands the kernel came out with 637
+                // spilled registers instead of 94, four accumulator tiles of a pass going to scratch memory and back once per bone pair.
+                h8 z;
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) z[jj] = (_Float16)0.f;
+                asm volatile("" : "+v"(z));
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    oh[s] = z;
+                    ol[s] = z;
+                }
             } else {
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
@@ -850,7 +979,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
 #else
         run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_keep(bh, bl, HS_A1 + 3), no_store);   // lin3
 #endif
-        if ((HN_DBG(a) >> 8) == 3) return;   // phase timing aid
+        if ((HN_DBG(a) >> 8) == 3) return true;   // phase timing aid
         // ---- lin4 = [a4 | features] / sqrt2 -> a5: 8 hidden tiles (bias from the tail), then the feature pass
         {
             f32x16 c1[8], c2[8];
@@ -922,10 +1051,10 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         sdf = (S16 ? sample_sum(sdf_acc, sdf_acc1) : half_sum(sdf_acc)) + a.b8[0];
         if (!FULL) {
             if (valid && h == 0) a.sdf[n] = sdf;
-            continue;
+            return false;
         }
 
-        if ((HN_DBG(a) >> 8) == 5) return;   // phase timing aid
+        if ((HN_DBG(a) >> 8) == 5) return true;   // phase timing aid
         // ---- lin8 rows 1..256: the feature vector (no activation) -> stash as fragments for colour lin0
         run_layer_c<8, 16, 1, true, true, HB_HID, HB_BWD, PH>(
             ws, bh, bl, lane, h, no_pre, PhIdentity{},
@@ -949,7 +1078,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             },
             no_store);
 
-        if ((HN_DBG(a) >> 8) == 6) return;   // phase timing aid
+        if ((HN_DBG(a) >> 8) == 6) return true;   // phase timing aid
         // ---- reverse sweep: dz_{l-1} = sigma'(z_{l-1}) * (W_l^T dz_l); sigma' from the stashed activation a_l
         auto act_of = [&](int act_slot) {
 #if defined(HN_STASH_HALF) && HN_STASH_HALF
@@ -1001,7 +1130,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, act_of(HS_A1 + 1), PhDsig{}, to_regs_t(ah, al, HS_DZ + 1), no_store);   // W2^T -> dz1
         run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 0), PhDsig{}, to_regs_t(bh, bl, HS_DZ + 0), no_store);   // W1^T -> dz0
 
-        if ((HN_DBG(a) >> 8) == 7) return;   // phase timing aid
+        if ((HN_DBG(a) >> 8) == 7) return true;   // phase timing aid
         // ---- d sdf / d features contracted with the encoding Jacobian, bone by bone: first W0^T dz0 (dz0 is in
         //      bh/bl), then W4[:, 256:]^T dz4 (reloaded into ah/al)
         // G = W0^T dz0 + W4[:, 256:]^T dz4 accumulated per tile (chunks alternate between the two matrices),
@@ -1037,6 +1166,10 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     ws.template begin_c<HB_BWD>();   // after the last one: bone 0's first chunk
                     mma_tile<16, 0, HB_BWD, PJ>(ws, buf4, ah, al, L1[u], L2[u], lane);
                 });
+                if constexpr (FAR) {
+                    // (no bone is live: nothing is kept of the block.  Its MFMAs run all the same -- dense compute -- so their results are used)
+                    asm volatile("" ::"v"(L1[0]), "v"(L2[0]), "v"(L1[1]), "v"(L2[1]));
+                } else {
                 f32x16 La = combine(L1[0], L2[0]), Lb = combine(L1[1], L2[1]);
                 tile_out(La);
                 tile_out(Lb);
@@ -1044,6 +1177,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     constexpr int b = decltype(B_)::value;
                     if ((nz >> b) & 1u) sh.f32_store(LEFTJ + b * 256, b < 16 ? La[b] : Lb[b - 16]);
                 });
+                }
             }
             const int jbase = ws.goff - HB_BWD;   // stream offset of bone 0's first chunk (in flight)
             unsigned rem = nzw & ~1u;
@@ -1053,9 +1187,13 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 const int nb = rem ? __builtin_ctz(rem) : N_BONES;   // the next bone that is run (21: what follows the bones: colour lin0's first chunk, the same size)
                 rem &= rem - 1u;
                 f32x16 G1[2], G2[2];
-                const bool live = (nz >> b) & 1u;
-                // the bone's row of the leftover block: requested four chunks ahead of its use
-                const float Gl = live ? sh.f32_load(LEFTJ + b * 256) : 0.f;
+                bool live = false;   // (the all-far program: no bone is, at compile time -- no staging, no contraction, the MFMAs alone)
+                [[maybe_unused]] float Gl = 0.f;
+                if constexpr (!FAR) {
+                    live = (nz >> b) & 1u;
+                    // the bone's row of the leftover block: requested four chunks ahead of its use
+                    Gl = live ? sh.f32_load(LEFTJ + b * 256) : 0.f;
+                }
                 static_for<2>([&](auto U) {
                     constexpr int u = decltype(U)::value;
                     const char* buf0 = ws.template acquire<0>();
@@ -1063,11 +1201,13 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     // the bone's own features go stash -> LDS by DMA (no registers: loaded into VGPRs here they
                     // are spilled one load at a time, 8 serialised round trips per bone); they land under the
                     // bone's MFMAs, the next acquire's vmcnt(0) covers them
+                    if constexpr (!FAR) {
                     if (u == 0 && live) {
 #pragma unroll
                         for (int i = 0; i < 8; ++i)
                             __builtin_amdgcn_raw_ptr_buffer_load_lds(sh.rsrc, (lds_void_t*)(stage + i * 1024), 16, lane_x16(),
                                                                      FEAT + (4 * b + (i >> 1)) * KS_BYTES + (i & 1) * 1024, 0, STASH_AUX);
+                    }
                     }
                     G1[u] = zero16();
                     G2[u] = zero16();
@@ -1077,7 +1217,9 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     ws.template begin_c<HB_BWD>();
                     mma_tile<16, 0, HB_BWD, PJ>(ws, buf4, ah, al, G1[u], G2[u], lane);
                 });
-                if (live) {   // a bone whose mask is 0 for the whole wave contributes exactly 0
+                if constexpr (FAR) {
+                    asm volatile("" ::"v"(G1[0]), "v"(G2[0]), "v"(G1[1]), "v"(G2[1]));   // (the results of MFMAs that run for the dense count)
+                } else if (live) {   // a bone whose mask is 0 for the whole wave contributes exactly 0
                     const Bone2 bn = coords(b);
                     const float kk = -TAU2 * (1.f - bn.hh);
                     float own[4][8];
@@ -1133,10 +1275,12 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 b = nb;
             }
         }
+        // (the all-far program: d sdf / d p is +0, as a run-time value -- enc(g) below is computed by the same instructions in both programs)
+        if constexpr (FAR) asm volatile("" : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]));
 #pragma unroll
         for (int c = 0; c < 3; ++c) g[c] *= BWD_INV;
 
-        if ((HN_DBG(a) >> 8) == 8) return;   // phase timing aid
+        if ((HN_DBG(a) >> 8) == 8) return true;   // phase timing aid
         // ---- colour lin0 = [features | feature vector | enc(g)] -> relu: per pass 4 feature-vector tiles, the
         //      feature block, then the enc(g) chunk (whose tail holds the 4 biases)
         h8 gh[2], gl[2];
@@ -1229,7 +1373,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     for (int i = lane; i < N_BONES * 12; i += 64) row[f * (N_BONES * 12) + i] = prow[f * POSE_ROW + i];
                 __builtin_amdgcn_wave_barrier();
             }
-            continue;
+            return false;
         }
         if (valid && h == 0) {
             a.sdf[n] = sdf;
@@ -1239,6 +1383,13 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             a.rgb[3 * n] = rgb[0];
             a.rgb[3 * n + 1] = rgb[1];
             a.rgb[3 * n + 2] = rgb[2];
+        }
+        return false;
+        };   // program
+        if constexpr (FAR_ARM) {
+            if (far ? program(std::true_type{}) : program(std::false_type{})) return;
+        } else {
+            if (program(std::false_type{})) return;
         }
     }
 }
@@ -1361,10 +1512,10 @@ static void hand2_common_args(Hand2Args& a, const hn_field* f, const float* pts,
 #elif defined(HN_HAND_F16_TU)   // hn_field2_hand_f16.hip: the evaluation kernels of HN_PREC_F16 (single-pass hidden layers)
 int launch_field2_hand_f16(const Hand2Args& a, int grid, bool full, hipStream_t stream) {
     static std::atomic<uint64_t> lds_full{0}, lds_sdf{0};
-    HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_hand_f16<1>), (int)HAND2_LDS, &lds_full));
+    HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_hand_f16<1>), (int)HAND2_LDS_EVAL, &lds_full));
     HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_hand_f16<0>), (int)HAND2_LDS, &lds_sdf));
     if (full)
-        hipLaunchKernelGGL(k_field2_hand_f16<1>, dim3(grid), dim3(256), HAND2_LDS, stream, a);
+        hipLaunchKernelGGL(k_field2_hand_f16<1>, dim3(grid), dim3(256), HAND2_LDS_EVAL, stream, a);
     else
         hipLaunchKernelGGL(k_field2_hand_f16<0>, dim3(grid), dim3(256), HAND2_LDS, stream, a);
     HN_LAUNCH_CHECK();
@@ -1411,6 +1562,7 @@ int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const flo
     a.feat = feat;
     const int us_mode = full ? uniform_stash_mode() : 0;   // (the full evaluation kernels alone are built with it)
     a.ustash = us_mode == 0 ? 0 : (us_mode == 2 ? USTASH_COLS : (USTASH_COLS | USTASH_SHIFT));
+    a.far_tiles = (us_mode == 1 && far_tiles_mode() != 0) ? 1 : 0;   // (the all-far tile program goes with the default, packed form)
 #ifdef HN_DEBUG_HOOKS
     {
         const char* e = getenv("HN_DBG");
@@ -1438,10 +1590,10 @@ int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const flo
     }
     if (single_pass) return launch_field2_hand_f16(a, grid, full, stream);
     static std::atomic<uint64_t> lds_full{0}, lds_sdf{0};   // devices on which the LDS size attribute is set
-    HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_hand<1>), (int)HAND2_LDS, &lds_full));
+    HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_hand<1>), (int)HAND2_LDS_EVAL, &lds_full));
     HN_TRY_RC(ensure_dynamic_lds(reinterpret_cast<const void*>(k_field2_hand<0>), (int)HAND2_LDS, &lds_sdf));
     if (full)
-        hipLaunchKernelGGL(k_field2_hand<1>, dim3(grid), dim3(256), HAND2_LDS, stream, a);
+        hipLaunchKernelGGL(k_field2_hand<1>, dim3(grid), dim3(256), HAND2_LDS_EVAL, stream, a);
     else
         hipLaunchKernelGGL(k_field2_hand<0>, dim3(grid), dim3(256), HAND2_LDS, stream, a);
     HN_LAUNCH_CHECK();
