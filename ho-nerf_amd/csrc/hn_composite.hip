@@ -3,11 +3,9 @@
 // (element e = lane + 64 m, so every load/store instruction touches 64 consecutive floats),
 // an inclusive product scan across the lanes per 64-sample segment and a scalar carry between
 // segments.  These kernels are HBM-bound: 24 B (single) / 40 B (dual) per ray-sample.
-#include "hn_common.h"
+#include "hn_scan.h"   // alpha_sample, the scans and run loads (shared with hn_gbuffer.hip)
 
 namespace hn {
-
-__device__ __forceinline__ float sigmoid_e(float x) { return 1.f / (1.f + expf(-x)); }
 
 __global__ void k_alpha(const float* __restrict__ sdf, const float* __restrict__ grad, const float* __restrict__ rays_d,
                         const float* __restrict__ dists, int n, int spr, float inv_s_host, float* __restrict__ alpha,
@@ -16,31 +14,12 @@ __global__ void k_alpha(const float* __restrict__ sdf, const float* __restrict__
     if (i >= n) return;
     const float inv_s = inv_s_dev != nullptr ? inv_s_dev[0] : inv_s_host;   // (hn_field_set_inv_s_device: a trained value that never visits the host)
     const int ray = i / spr;
-    const float true_cos = rays_d[3 * ray] * grad[3 * (size_t)i] + rays_d[3 * ray + 1] * grad[3 * (size_t)i + 1] +
-                           rays_d[3 * ray + 2] * grad[3 * (size_t)i + 2];
-    const float iter_cos = -fmaxf(-true_cos, 0.f);     // cos_anneal_ratio = 1
-    const float s = sdf[i];
-    const float half = iter_cos * dists[i] * 0.5f;
-    const float c = sigmoid_e((s - half) * inv_s);
-    const float nx = sigmoid_e((s + half) * inv_s);
-    const float a = ((c - nx) + 1e-5f) / (c + 1e-5f);
-    alpha[i] = fminf(fmaxf(a, 0.f), 1.f);
+    float c;
+    alpha[i] = alpha_sample(rays_d[3 * ray], rays_d[3 * ray + 1], rays_d[3 * ray + 2], grad[3 * (size_t)i], grad[3 * (size_t)i + 1],
+                            grad[3 * (size_t)i + 2], sdf[i], dists[i], inv_s, c);
     if (c_out != nullptr) c_out[i] = c;
 }
 
-__device__ __forceinline__ float wave_incl_prod(float v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float o = __shfl_up(v, off, 64);
-        if (lane >= off) v *= o;
-    }
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
@@ -190,11 +169,7 @@ __global__ __launch_bounds__(256) void k_composite2(const float* __restrict__ ah
 // 4 g + r, so a wave reads 4*S consecutive floats of every per-sample array with 16-byte loads.  The transmittance is a
 // sequential product inside the lane, an exclusive product scan over the 16 lanes of the row (DPP row_shr: VALU only,
 // where __shfl_up goes through the LDS crossbar) and the per-ray sums are row_ror butterflies.
-template <int CTRL>
-__device__ __forceinline__ float dpp(float old, float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL,
-                                                                  0xf, 0xf, false));
-}
+// (dpp, load_run, group_sum and group_excl_prod: hn_scan.h)
 // inclusive product over the 16 lanes of a row (row_shr:n = 0x110 + n; lanes without a source keep `old` = 1)
 __device__ __forceinline__ float row_incl_prod(float v) {
     v *= dpp<0x111>(1.f, v);
@@ -218,18 +193,6 @@ __device__ __forceinline__ float row_max(float v) {
     v = fmaxf(v, dpp<0x121>(0.f, v));
     return v;
 }
-// loads CPS consecutive floats / CPS consecutive float3 of this lane (16-byte accesses)
-template <int CPS>
-__device__ __forceinline__ void load_run(const float* __restrict__ p, float (&v)[CPS]) {
-#pragma unroll
-    for (int q = 0; q < CPS / 4; ++q) {
-        const float4 t = reinterpret_cast<const float4*>(p)[q];
-        v[4 * q] = t.x;
-        v[4 * q + 1] = t.y;
-        v[4 * q + 2] = t.z;
-        v[4 * q + 3] = t.w;
-    }
-}
 template <int CPS>
 __device__ __forceinline__ void store_run(float* __restrict__ p, const float (&v)[CPS]) {
 #pragma unroll
@@ -241,16 +204,7 @@ __device__ __forceinline__ float wave_sum_rows(float v) {   // v is already a ro
     return v;
 }
 
-// sum / max over a group of LPR (8 or 16) consecutive lanes, result in every lane of the group: xor butterflies as DPP
-// (quad_perm [1,0,3,2] = 0xB1, [2,3,0,1] = 0x4E, row_half_mirror = 0x141, row_mirror = 0x140): VALU only
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-    v += dpp<0xB1>(0.f, v);
-    v += dpp<0x4E>(0.f, v);
-    v += dpp<0x141>(0.f, v);
-    if (LPR == 16) v += dpp<0x140>(0.f, v);
-    return v;
-}
+// max over a group of LPR (8 or 16) consecutive lanes, result in every lane of the group (as group_sum, hn_scan.h)
 template <int LPR>
 __device__ __forceinline__ float group_max(float v) {
     v = fmaxf(v, dpp<0xB1>(0.f, v));
@@ -258,20 +212,6 @@ __device__ __forceinline__ float group_max(float v) {
     v = fmaxf(v, dpp<0x141>(0.f, v));
     if (LPR == 16) v = fmaxf(v, dpp<0x140>(0.f, v));
     return v;
-}
-// exclusive product scan over the group (lane l of the group gets the product of lanes 0 .. l-1; lane 0 gets 1)
-template <int LPR>
-__device__ __forceinline__ float group_excl_prod(float v, int l) {
-    float t;
-    t = dpp<0x111>(1.f, v);
-    v *= (LPR == 16 || l >= 1) ? t : 1.f;
-    t = dpp<0x112>(1.f, v);
-    v *= (LPR == 16 || l >= 2) ? t : 1.f;
-    t = dpp<0x114>(1.f, v);
-    v *= (LPR == 16 || l >= 4) ? t : 1.f;
-    if (LPR == 16) v *= dpp<0x118>(1.f, v);
-    t = dpp<0x111>(1.f, v);          // shift the inclusive scan by one lane
-    return l >= 1 ? t : 1.f;
 }
 template <int N>
 __device__ __forceinline__ float eik_run(const float (&x)[3 * N]) {
@@ -691,12 +631,6 @@ __global__ __launch_bounds__(256) void k_composite1_bwd_wave(const float* __rest
         P = a[j] * u[j] + f[j] * P;
         if (k < S) g_c[base + k] = k == 0 ? P : 0.f;   // dL/dseed = P_{-1}: T_k is linear in the seed c_0
     }
-}
-
-// 4 rays per block; at most 8 blocks per CU, grid-stride beyond that
-static int composite_grid(int n_rays) {
-    const int blocks = (n_rays + 3) / 4;
-    return blocks < 2048 ? blocks : 2048;
 }
 
 int alpha(const float* sdf, const float* grad, const float* rays_d, const float* dists, int n, int spr, float inv_s,

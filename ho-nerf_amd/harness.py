@@ -95,6 +95,47 @@ def render_views(renderer, cameras, H, W, near, far, bt_inv, T_pose_21, Ro, To, 
     return out
 
 
+def render_view_buffers(renderer, cameras, H, W, near, far, bt_inv, T_pose_21, Ro, To, batch_size=16384, t_rand=None, opacity_threshold=0.5):
+    """`render_views` with the geometry buffers next to the colour: the same cameras, rays, chunks and `t_rand`, through
+    `renderer.render_buffers` under torch.no_grad().  Returns device tensors, with opacity = opacity_hand + opacity_obj per pixel:
+      color  uint8 [V, H, W, 3]    `render_views`' bits
+      depth  float32 [V, H, W]     depth / opacity where opacity >= opacity_threshold, else 0
+      normal uint8 [V, H, W, 3]    the composited normal in the CAMERA frame (row vectors, SURVEY 8c: n_view = n_world @ R), normalised,
+                                   (n * 0.5 + 0.5) * 255 clamped and truncated; 0 where opacity < opacity_threshold
+      label  uint8 [V, H, W]       0 where opacity < opacity_threshold, else 1 (hand) if opacity_hand >= opacity_obj, else 2 (object)"""
+    device = torch.device('cuda')
+    cams = {k: np.asarray(cameras[k], dtype=np.float32) for k in ('R', 'T', 'focal', 'principal')}
+    V = cams['R'].shape[0]
+    if cams['R'].shape != (V, 3, 3) or cams['T'].shape != (V, 3) or cams['focal'].shape != (V, 2) or cams['principal'].shape != (V, 2):
+        raise ValueError('render_view_buffers: cameras must hold R [V,3,3], T [V,3], focal [V,2], principal [V,2]')
+    B, step = H * W, int(batch_size)
+    if step < 1:
+        raise ValueError('render_view_buffers: batch_size = %d' % step)
+    if t_rand is not None and tuple(t_rand.shape) != (V, B, 1):
+        raise ValueError('render_view_buffers: t_rand is %s, expected [%d, %d, 1]' % (tuple(t_rand.shape), V, B))
+    Ro_t = torch.as_tensor(Ro, dtype=torch.float32, device=device).T.contiguous()
+    To = torch.as_tensor(To, dtype=torch.float32, device=device)
+    out = {'color': torch.empty(V, H, W, 3, dtype=torch.uint8, device=device), 'depth': torch.empty(V, H, W, device=device),
+           'normal': torch.empty(V, H, W, 3, dtype=torch.uint8, device=device), 'label': torch.empty(V, H, W, dtype=torch.uint8, device=device)}
+    with torch.no_grad():
+        for v in range(V):
+            rays_o, rays_d = image_rays({k: a[v:v + 1] for k, a in cams.items()}, H, W, device)
+            R = torch.from_numpy(cams['R'][v]).to(device)
+            color, depth, normal, label = out['color'][v].view(B, 3), out['depth'][v].view(B), out['normal'][v].view(B, 3), out['label'][v].view(B)
+            for s in range(0, B, step):
+                kw = {} if t_rand is None else {'t_rand': t_rand[v, s:s + step]}
+                o = renderer.render_buffers(rays_o[s:s + step], rays_d[s:s + step], near, far, bt_inv, T_pose_21, None, Ro_t, To, **kw)
+                color[s:s + step] = (o['color_fine'].detach().float().reshape(-1, 3) * 255.0).clamp(0, 255).to(torch.uint8)
+                oh, oo = o['opacity_hand'].reshape(-1), o['opacity_obj'].reshape(-1)
+                opacity = oh + oo
+                seen = opacity >= opacity_threshold
+                depth[s:s + step] = torch.where(seen, o['depth'].reshape(-1) / opacity, torch.zeros_like(opacity))
+                n = torch.nn.functional.normalize(o['normal'].reshape(-1, 3) @ R, dim=-1)
+                normal[s:s + step] = ((n * 0.5 + 0.5) * 255.0).clamp(0, 255).to(torch.uint8) * seen[:, None]
+                label[s:s + step] = torch.where(seen, torch.where(oh >= oo, 1, 2), 0).to(torch.uint8)
+    return out
+
+
 # ---- image files: binary PPM by our own code (always there), anything else through PIL when it imports ---------------------------
 def write_image(path, img):
     """uint8 [H, W, 3] (array or tensor) -> a file.  `.ppm`: binary PPM (P6, maxval 255), the channels stored as they are in the array.
@@ -119,8 +160,20 @@ def read_image(path):
             return np.ascontiguousarray(np.asarray(im.convert('RGB'), dtype=np.uint8))
     with open(path, 'rb') as f:
         data = f.read()
-    if data[:2] != b'P6':
-        raise ValueError('%s: not a binary PPM (magic %r)' % (path, data[:2]))
+    w, h, maxval, pos = _pnm_header(path, data, b'P6', 'PPM')
+    if maxval != 255:
+        raise ValueError('%s: maxval %d, only 8-bit PPM (maxval 255) is read' % (path, maxval))
+    if w < 1 or h < 1:
+        raise ValueError('%s: a %d x %d image' % (path, w, h))
+    if len(data) - pos < 3 * w * h:
+        raise ValueError('%s: truncated: %d bytes of pixels, %d x %d x 3 = %d expected' % (path, len(data) - pos, w, h, 3 * w * h))
+    return np.frombuffer(data, dtype=np.uint8, count=3 * w * h, offset=pos).reshape(h, w, 3).copy()
+
+
+def _pnm_header(path, data, magic, kind):
+    """The header of a binary PPM / PGM file's bytes -> (width, height, maxval, offset of the raster)."""
+    if data[:2] != magic:
+        raise ValueError('%s: not a binary %s (magic %r)' % (path, kind, data[:2]))
     pos, fields = 2, []
     while len(fields) < 3:                                      # width, height, maxval: decimal, separated by whitespace / comments
         while pos < len(data) and (data[pos:pos + 1].isspace() or data[pos:pos + 1] == b'#'):
@@ -133,20 +186,58 @@ def read_image(path):
         while end < len(data) and data[end:end + 1].isdigit():
             end += 1
         if end == pos:
-            raise ValueError('%s: truncated or malformed PPM header' % path)
+            raise ValueError('%s: truncated or malformed %s header' % (path, kind))
         fields.append(int(data[pos:end]))
         pos = end
     if not data[pos:pos + 1].isspace():
-        raise ValueError('%s: truncated or malformed PPM header' % path)
-    pos += 1                                                    # the single whitespace byte before the raster
-    w, h, maxval = fields
-    if maxval != 255:
-        raise ValueError('%s: maxval %d, only 8-bit PPM (maxval 255) is read' % (path, maxval))
+        raise ValueError('%s: truncated or malformed %s header' % (path, kind))
+    return fields[0], fields[1], fields[2], pos + 1             # (the single whitespace byte before the raster)
+
+
+# ---- single-channel images: binary PGM (P5), 8 bit for the label maps, 16 bit for depth in millimetres --------------------------------
+def write_gray(path, img):
+    """uint8 or uint16 [H, W] (array or tensor) -> a binary PGM (P5; maxval 255, or 65535 with the samples big-endian, as the format
+    says)."""
+    a = _host(img)
+    if a.dtype not in (np.uint8, np.uint16) or a.ndim != 2 or a.size == 0:
+        raise ValueError('write_gray: expected a non-empty uint8 or uint16 [H, W] image, got %s %s' % (a.dtype, a.shape))
+    with open(path, 'wb') as f:
+        f.write(b'P5\n%d %d\n%d\n' % (a.shape[1], a.shape[0], 255 if a.dtype == np.uint8 else 65535))
+        f.write(np.ascontiguousarray(a).astype('>u2' if a.dtype == np.uint16 else np.uint8).tobytes())
+
+
+def read_gray(path):
+    """The binary PGM `write_gray` writes -> uint8 (maxval 255) or uint16 (maxval 65535) [H, W] numpy; comments in the header are
+    allowed."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    w, h, maxval, pos = _pnm_header(path, data, b'P5', 'PGM')
+    if maxval not in (255, 65535):
+        raise ValueError('%s: maxval %d, only 8-bit (255) and 16-bit (65535) PGM is read' % (path, maxval))
     if w < 1 or h < 1:
         raise ValueError('%s: a %d x %d image' % (path, w, h))
-    if len(data) - pos < 3 * w * h:
-        raise ValueError('%s: truncated: %d bytes of pixels, %d x %d x 3 = %d expected' % (path, len(data) - pos, w, h, 3 * w * h))
-    return np.frombuffer(data, dtype=np.uint8, count=3 * w * h, offset=pos).reshape(h, w, 3).copy()
+    size = 1 if maxval == 255 else 2
+    if len(data) - pos < size * w * h:
+        raise ValueError('%s: truncated: %d bytes of pixels, %d x %d x %d = %d expected' % (path, len(data) - pos, w, h, size, size * w * h))
+    a = np.frombuffer(data, dtype=np.uint8 if size == 1 else '>u2', count=w * h, offset=pos).reshape(h, w)
+    return a.astype(np.uint8 if size == 1 else np.uint16)
+
+
+def write_depth(path, depth_m):
+    """float [H, W] depth in metres (array or tensor) -> a 16-bit PGM in millimetres, rounded to nearest and clamped to 65535; 0 stays
+    0, "no surface" (render_view_buffers)."""
+    a = np.asarray(_host(depth_m), dtype=np.float64)
+    if a.ndim != 2 or a.size == 0 or not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError('write_depth: expected a non-empty [H, W] image of finite depths >= 0, got %s' % (a.shape,))
+    write_gray(path, np.minimum(np.rint(a * 1000.0), 65535.0).astype(np.uint16))
+
+
+def read_depth(path):
+    """The file `write_depth` writes -> float32 [H, W] metres (0: no surface)."""
+    a = read_gray(path)
+    if a.dtype != np.uint16:
+        raise ValueError('%s: a depth file is a 16-bit PGM' % path)
+    return a.astype(np.float32) / np.float32(1000.0)
 
 
 def _pil(path):

@@ -264,6 +264,37 @@ class NeuSRenderer:
             'gradient_error': gerr.reshape(()),
         }
 
+    def render_buffers(self, rays_o, rays_d, near, far, bt_inv, T_pose_21, verts, Ro, To, index, t_rand=None):
+        """`render`'s dictionary plus the geometry the renderer holds per ray (hn_gbuffer1): `opacity` [B,1] (= weight_sum), `depth`
+        [B,1] = sum_k w_k m_k over the section mid-points (NOT divided by the opacity) and `normal` [B,3] = sum_k w_k grad_k in the
+        world frame (an object field's gradient lives in its own frame p' = Ro (p - To): Ro^T n brings the sum back).  The launches
+        of `render`, then the field at the final depths once more -- hn_render_single keeps no per-sample output -- and one
+        hn_gbuffer1 launch.  No tape, no graph: an input that requires grad is refused."""
+        if _wants_grad(rays_o, rays_d, bt_inv, T_pose_21, Ro, To):
+            raise ValueError('render_buffers builds no graph: an input requires grad; differentiate through render')
+        with torch.no_grad():
+            out = dict(self.render(rays_o, rays_d, near, far, bt_inv, T_pose_21, verts, Ro, To, index, t_rand=t_rand))
+            f, lib = self.field(), self.lib
+            z = self.last_z_vals
+            B, S = z.shape
+            dev = z.device
+            ro, rd = _lib.f32(rays_o).reshape(-1, 3), _lib.f32(rays_d).reshape(-1, 3)
+            if self.model_type == 'obj':
+                ro, rd = self.convert_obj_to_local(ro, rd, Ro, To)
+            sample_dist = (float(far) - float(near)) / self.n_samples
+            pts, _ = _points(lib, ro, rd, z, 1, sample_dist)
+            if self.model_type == 'hand':
+                sdf, grad, _ = f.evaluate(pts, rd, S, _lib.f32(bt_inv, dev).reshape(1, 21, 4, 4), _lib.f32(T_pose_21, dev).reshape(1, 21, 3))
+            else:
+                sdf, grad, _ = f.evaluate(pts, rd, S)
+            opacity, depth, normal = torch.empty(B, 1, device=dev), torch.empty(B, 1, device=dev), torch.empty(B, 3, device=dev)
+            _lib.check(lib.hn_gbuffer1(_lib.ptr(sdf), _lib.ptr(grad), _lib.ptr(rd), _lib.ptr(z), B, S, sample_dist, float(f.inv_s),
+                                       _lib.ptr(opacity), _lib.ptr(depth), _lib.ptr(normal), _lib.stream_ptr()), 'hn_gbuffer1')
+            if self.model_type == 'obj':
+                normal = normal @ _lib.f32(Ro, dev).reshape(3, 3)         # row vectors: Ro^T n
+            out.update(opacity=opacity, depth=depth, normal=normal)
+            return out
+
     def sdf(self, pts, bt_inv=None, T_pose_21=None):
         """The SDF grid queries of extract_geometry (utils/renderer.py:260-278) in one launch."""
         return self.field().sdf(pts, bt_inv, T_pose_21)
@@ -446,6 +477,44 @@ class NeuSRenderer_fitting:
             'gradient_hand': o['grad_hand'],
             'gradient_obj': o['grad_obj'],
         }
+
+    def render_buffers(self, rays_o, rays_d, near, far, bt_inv, T_pose_21, verts, Ro, To, get_SDF=False, t_rand=None):
+        """`render`'s dictionary plus the geometry the renderer holds per ray, from that render's own per-sample sdf / gradients and
+        final depths in one launch (hn_gbuffer2; the object's ray directions through hn_obj_local_fwd first):
+          opacity_hand, opacity_obj [B,1]      sum_k w^f_k (their sum is weight_sum)
+          depth_hand, depth_obj, depth [B,1]   sum_k w^f_k m_k over the section mid-points, and the sum over the fields: NOT divided by
+                                               the opacity (the expected depth of a pixel is depth / (opacity_hand + opacity_obj))
+          normal_hand, normal_obj, normal [B,3] sum_k w^f_k grad^f_k in the world frame, and the sum over the fields
+        ([F,P,..] for the frame-batched class).  No tape, no graph: an input that requires grad is refused."""
+        if _wants_grad(rays_o, rays_d, bt_inv, T_pose_21, Ro, To):
+            raise ValueError('render_buffers builds no graph: an input requires grad; differentiate through render')
+        with torch.no_grad():
+            out = dict(self.render(rays_o, rays_d, near, far, bt_inv, T_pose_21, verts, Ro, To, get_SDF, t_rand=t_rand))
+            hand, obj = self.fields()
+            ro, rd = _lib.f32(rays_o), _lib.f32(rays_d)
+            if not self.batched:
+                ro, rd = ro.reshape(1, -1, 3), rd.reshape(1, -1, 3)
+            F, P = ro.shape[0], ro.shape[1]
+            N, dev = F * P, ro.device
+            z = self._last_z_raw
+            S = z.shape[1]
+            ro, rd = ro.reshape(N, 3), rd.reshape(N, 3)
+            Ro_, To_ = _lib.f32(Ro, dev).reshape(F, 3, 3), _lib.f32(To, dev).reshape(F, 3)
+            o2, d2 = torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev)
+            st = _lib.stream_ptr()
+            _lib.check(self.lib.hn_obj_local_fwd(_lib.ptr(ro), _lib.ptr(rd), _lib.ptr(Ro_), _lib.ptr(To_), F, P, _lib.ptr(o2), _lib.ptr(d2), st),
+                       'hn_obj_local_fwd')
+            opacity, depth, normal = torch.empty(N, 2, device=dev), torch.empty(N, 2, device=dev), torch.empty(N, 2, 3, device=dev)
+            _lib.check(self.lib.hn_gbuffer2(_lib.ptr(out['sdf_hand']), _lib.ptr(out['gradient_hand']), _lib.ptr(rd), float(hand.inv_s),
+                                            _lib.ptr(out['sdf_obj']), _lib.ptr(out['gradient_obj']), _lib.ptr(d2), float(obj.inv_s), _lib.ptr(z),
+                                            F, P, S, (float(far) - float(near)) / self.n_samples, _lib.ptr(Ro_), _lib.ptr(opacity),
+                                            _lib.ptr(depth), _lib.ptr(normal), st), 'hn_gbuffer2')
+            lead = (F, P) if self.batched else (N,)
+            out.update(opacity_hand=opacity[:, 0].reshape(*lead, 1), opacity_obj=opacity[:, 1].reshape(*lead, 1),
+                       depth_hand=depth[:, 0].reshape(*lead, 1), depth_obj=depth[:, 1].reshape(*lead, 1),
+                       depth=depth.sum(-1).reshape(*lead, 1), normal_hand=normal[:, 0].reshape(*lead, 3),
+                       normal_obj=normal[:, 1].reshape(*lead, 3), normal=normal.sum(1).reshape(*lead, 3))
+            return out
 
     def _render_autograd(self, rays_o, rays_d, near, far, bt_inv, T_pose_21, Ro, To, t_rand, lead):
         """The same render with the outputs attached to the autograd graph of the pose-dependent inputs

@@ -368,6 +368,25 @@ int hn_composite2_bwd(const float* alpha_h, const float* rgb_h, const float* alp
                       const float* g_color, const float* g_weight_sum, int n_rays, int S, float* g_alpha_h,
                       float* g_rgb_h, float* g_alpha_o, float* g_rgb_o, hn_stream_t stream);
 
+/* ---- geometry buffers (hn_gbuffer.hip): per ray where the surface is, which way it faces and whose it is ------------------
+ * From the per-sample sdf [N*S] / gradient [N*S,3] of a render (hn_render_dual's sdf_*, grad_*; hn_field_eval's for one field),
+ * its depths z_vals [N,S] (the section STARTS, as hn_render_* return them) and the ray directions in each field's frame
+ * (rays_d_obj: what hn_obj_local_fwd gives), in one launch that writes neither alpha nor weights:
+ *   dist_k = z_{k+1} - z_k (the last one sample_dist), m_k = z_k + dist_k / 2, alpha_k as hn_alpha computes it;
+ *   two fields: T_k = prod_{j<k} (1 - a^h_j + 1e-7)(1 - a^o_j + 1e-7); one field: T_k = c_0 prod_{j<k} (1 - a_j + 1e-7);
+ *   w^f_k = a^f_k T_k;  opacity = sum_k w^f_k;  depth = sum_k w^f_k m_k (NOT divided by the opacity);  normal = sum_k w^f_k grad^f_k.
+ * hn_gbuffer1: opacity [N], depth [N], normal [N,3].  hn_gbuffer2 (N = n_frames * rays_per_frame): opacity [N,2], depth [N,2],
+ * normal [N,2,3], hand then obj; the object's normal is rotated back to the world frame as Ro^T n with the frame's Ro
+ * [n_frames,3,3] (the matrix of hn_obj_local_fwd); Ro NULL leaves it in the object's frame.  Every output may be NULL: it is then
+ * neither computed nor written.  Nothing allocates or synchronises and there is no workspace.  S < 1, a negative count or a
+ * NULL input is HN_EINVAL with a message, before anything is launched; N = 0 launches nothing and returns 0. */
+int hn_gbuffer1(const float* sdf, const float* grad, const float* rays_d, const float* z_vals, int n_rays, int S, float sample_dist,
+                float inv_s, float* opacity, float* depth, float* normal, hn_stream_t stream);
+int hn_gbuffer2(const float* sdf_hand, const float* grad_hand, const float* rays_d_hand, float inv_s_hand,
+                const float* sdf_obj, const float* grad_obj, const float* rays_d_obj, float inv_s_obj,
+                const float* z_vals, int n_frames, int rays_per_frame, int S, float sample_dist, const float* Ro,
+                float* opacity, float* depth, float* normal, hn_stream_t stream);
+
 /* ---- whole renders ----------------------------------------------------------------------
  * NeuSRenderer.render (utils/renderer.py:190-258).  rays already in the field's frame
  * (obj: after hn_obj_local_fwd).  t_rand [B].  Outputs: color [B,3], cdf [B,S],
