@@ -4,35 +4,22 @@
 //
 // The model (hn_lpips_create) holds the 13 convolutions' weights packed once into MFMA fragment order, their biases and the five
 // 1x1 linear weight vectors.  A call runs the 2 F images (a's, then b's) through the whole stack as ONE batch: activations are
-// channel-last fp32 [N, h, w, C] in the caller's workspace, so the K axis of every convolution (tap-major: k = (3 ky + kx) Cin + c) is
-// contiguous in memory.  No allocation, no synchronisation, no floating-point atomics: every output element is one fmaf chain in a
-// fixed order that does not depend on where its tile lies, every reduction combines its partials in a fixed order per image, so a
-// repeated call, another batch size or another position in the batch give the same bits.
+// channel-last fp32 [N, h, w, C] in the caller's workspace.  No allocation, no synchronisation, no floating-point atomics: every
+// output element is one fmaf chain in a fixed order that does not depend on where its tile lies, every reduction combines its
+// partials in a fixed order per image, so a repeated call, another batch size or another position in the batch give the same bits.
 //
-// Precision: exact fp32, v_mfma_f32_32x32x2_f32 (each output = one fp32 fmaf chain over K, the bias added after it).  Activations of
-// trained VGG weights are not known here and nothing bounds them to fp16's range, which rules out fp16 operands without a per-layer
-// rescale; the fp32 MFMA needs none.
+// The convolution stack (packing, patch gather, exact-fp32 implicit GEMM, pool: k_cv_pack, k_cv_im2col, k_cv_conv, k_cv_pool) is
+// hn_conv3x3.h, shared with hn_vggloss.hip.  LPIPS runs it with all nine taps live and one K split for every layer and size.
 //
-// Kernels:
-//   k_lp_pack        [Cout, Cin, 3, 3] -> fragments [Cout / 32][Kpad / 8][64 lanes] float4: lane l holds W[n = 32 nt + (l & 31)]
-//                    [k = 8 g + 4 (l >> 5) + 0..3], zero for k >= 9 Cin (the first layer: K = 27 -> 32)
-//   k_lp_im2col      the scaling layer and the first layer's patch gather: u8 -> ((u8 / 128 - 1) - shift) / scale, the 27 values of
-//                    the 3 x 3 x 3 patch (zero outside the image, as the zero padding of the SCALED input is) + 5 zeros -> [N, H, W, 32]:
-//                    the first convolution then is the same kernel with one tap and Cin = 32
-//   k_lp_conv        implicit GEMM, 128 output pixels x 64 output channels per workgroup of 4 waves (2 x 2: a wave owns 64 pixels x 32
-//                    channels = two 32 x 32 accumulators), K in chunks of 32 channels of one tap.  A chunk's 128 x 32 activations
-//                    (zeros where the tap leaves the image) and its 64 x 32 weights go global -> registers -> LDS, the next chunk's
-//                    loads in flight while this chunk's 32 MFMAs per wave run, two LDS buffers, one barrier per chunk.  One
-//                    ds_read_b128 feeds 4 k-steps (lane half h takes k = 4 h + 0..3 of each group of 8: the order of k inside a
-//                    group is free as long as both operands agree).  The A tile's pitch of 36 floats keeps those reads free of bank
-//                    conflicts.  Epilogue: + bias, ReLU, 128-byte row stores.
-//   k_lp_pool        MaxPool2d(2, 2), floor mode: [N, h, w, C] -> [N, h / 2, w / 2, C]
+// Its own kernels:
+//   LpLoad           the scaling layer, as the patch gather's loader: u8 -> ((u8 / 128 - 1) - shift) / scale (the gather's zeros outside
+//                    the image are the zero padding of the SCALED input)
 //   k_lp_head        per pixel of a tap (one wave per pixel, lanes over channels): n(f) = f / (sqrt(sum_c f^2) + 1e-10) for both
 //                    images, sum_c w[c] (n(fa) - n(fb))^2 in fp32, summed over the wave's 16 pixels and the workgroup's 4 waves in fp64
 //                    -> one partial per 64 pixels
 //   k_lp_head_final  one wave per pair: strided sum of the partials, butterfly, the mean -> per_tap [F, 5]
 //   k_lp_nchw        a tap [N, h, w, C] -> torch's [N, C, h, w] (hn_lpips_features)
-#include "hn_common.h"
+#include "hn_conv3x3.h"
 
 struct hn_lpips_model {
     void* blob = nullptr;                // one device allocation: packed weights, biases, linear weights
@@ -44,8 +31,6 @@ struct hn_lpips_model {
 namespace hn {
 namespace {
 
-typedef float lp_f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int LP_CONVS = 13, LP_TAPS = 5;
 constexpr int LP_CIN[LP_CONVS] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
 constexpr int LP_COUT[LP_CONVS] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
@@ -53,165 +38,20 @@ constexpr int LP_TAP_C[LP_TAPS] = {64, 128, 256, 512, 512};
 constexpr int LP_MIN_SIDE = 16;                                   // the fifth tap is floor(H / 16) x floor(W / 16)
 constexpr long long LP_MAX = 1LL << 31;                           // N H W 64, the largest activation, stays below this
 
-constexpr int CV_BM = 128, CV_BN = 64, CV_KC = 32, CV_THREADS = 256;
-constexpr int CV_APITCH = CV_KC + 4;                              // floats; 36 l mod 64 is a different multiple of 4 for 16 lanes
-constexpr int CV_A_FLOATS = CV_BM * CV_APITCH;                    // per buffer
-constexpr int CV_B_FLOAT4 = (CV_BN / 32) * (CV_KC / 8) * 64;      // per buffer: 512 float4
-static_assert(CV_A_FLOATS * 4 * 2 + CV_B_FLOAT4 * 16 * 2 <= 64 * 1024, "static LDS");
-static_assert(CV_BM * (CV_KC / 4) == 4 * CV_THREADS && CV_B_FLOAT4 == 2 * CV_THREADS, "loads per thread and chunk");
-
 constexpr int HEAD_THREADS = 256, HEAD_PX_WAVE = 16, HEAD_PX = (HEAD_THREADS / 64) * HEAD_PX_WAVE;
 
-__host__ __device__ inline int lp_kpad(int cin) { return (9 * cin + CV_KC - 1) / CV_KC * CV_KC; }
-
-// ---- weights -----------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_lp_pack(const float* __restrict__ w, int cin, int cout, float* __restrict__ out) {
-    const int kpad = lp_kpad(cin), groups = kpad / 8;
-    const long long total = (long long)cout * kpad;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int j = (int)(i & 3), lane = (int)((i >> 2) & 63);
-    const long long fg = i >> 8;                                   // nt * groups + g
-    const int g = (int)(fg % groups), nt = (int)(fg / groups);
-    const int n = 32 * nt + (lane & 31), k = 8 * g + 4 * (lane >> 5) + j;
-    float v = 0.f;
-    if (k < 9 * cin) {
-        const int tap = k / cin, c = k - tap * cin;
-        v = w[((long long)n * cin + c) * 9 + tap];
+// ---- the scaling layer, inside the first layer's patch gather -------------------------------------------------------------------------
+struct LpLoad {
+    const unsigned char *a, *b;          // [., h, w, 3]: image f of a at f < n_a, of b at f - n_a
+    int n_a, h, w;
+    __device__ float operator()(int f, int yy, int xx, int c) const {
+        const unsigned char* img = f < n_a ? a + (long long)f * h * w * 3 : b + (long long)(f - n_a) * h * w * 3;
+        const float shift = c == 0 ? -0.030f : c == 1 ? -0.088f : -0.188f;
+        const float scale = c == 0 ? 0.458f : c == 1 ? 0.448f : 0.450f;
+        const float u = (float)img[((long long)yy * w + xx) * 3 + c] / 128.f - 1.f;          // exact
+        return (u - shift) / scale;
     }
-    out[i] = v;
-}
-
-// ---- the scaling layer + the first layer's patches -----------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_lp_im2col(const unsigned char* __restrict__ a, const unsigned char* __restrict__ b, int n_a, int n_img,
-                                                   int h, int w, float* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // (pixel m, quarter q): k = 4 q .. 4 q + 3
-    const long long M = (long long)n_img * h * w;
-    if (i >= M * 8) return;
-    const long long m = i >> 3;
-    const int q = (int)(i & 7);
-    const int f = (int)(m / ((long long)h * w));
-    const int rem = (int)(m - (long long)f * h * w), y = rem / w, x = rem - y * w;
-    const unsigned char* img = f < n_a ? a + (long long)f * h * w * 3 : b + (long long)(f - n_a) * h * w * 3;
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int k = 4 * q + j;
-        v[j] = 0.f;
-        if (k < 27) {
-            const int tap = k / 3, c = k - 3 * tap, yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
-            if (yy >= 0 && yy < h && xx >= 0 && xx < w) {
-                const float shift = c == 0 ? -0.030f : c == 1 ? -0.088f : -0.188f;
-                const float scale = c == 0 ? 0.458f : c == 1 ? 0.448f : 0.450f;
-                const float u = (float)img[((long long)yy * w + xx) * 3 + c] / 128.f - 1.f;          // exact
-                v[j] = (u - shift) / scale;
-            }
-        }
-    }
-    *(float4*)(out + i * 4) = make_float4(v[0], v[1], v[2], v[3]);
-}
-
-// ---- the convolution ---------------------------------------------------------------------------------------------------------------
-// in [n_img, h, w, cin] (cin a multiple of 32), taps = 9: 3 x 3, zero padding 1; taps = 1: the pixel itself.  out [n_img, h, w, cout].
-__global__ void __launch_bounds__(CV_THREADS) k_lp_conv(const float* __restrict__ in, const float4* __restrict__ wpk, const float* __restrict__ bias,
-                                                        float* __restrict__ out, int M, int h, int w, int cin, int cout, int taps) {
-    __shared__ __attribute__((aligned(16))) float sA[2][CV_A_FLOATS];
-    __shared__ float4 sB[2][CV_B_FLOAT4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
-    const int m0 = blockIdx.x * CV_BM, by = blockIdx.y;
-    const int cchunks = cin / CV_KC, n_chunks = taps * cchunks, groups = n_chunks * (CV_KC / 8);
-    // the four tile rows this thread stages: r = (t >> 3) + 32 i, floats 4 q .. 4 q + 3 of the chunk
-    const int q = t & 7;
-    int py[4], px[4];
-    bool pv[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + (t >> 3) + 32 * i;
-        pv[i] = m < M;
-        const int rem = pv[i] ? m % (h * w) : 0;
-        py[i] = rem / w;
-        px[i] = rem - py[i] * w;
-    }
-    lp_f32x16 acc[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
-    // step ch: fetch chunk ch + 1 into registers, run chunk ch from LDS buffer ch & 1, park the registers in the other buffer, barrier
-    // (that buffer was last read in step ch - 1, which every wave has left).  Step -1 only fetches and parks chunk 0.
-    for (int ch = -1; ch < n_chunks; ++ch) {
-        const int buf = ch & 1, nx = ch + 1;
-        const bool more = nx < n_chunks;
-        float4 ra0, ra1, ra2, ra3, rb0, rb1;
-        ra0 = ra1 = ra2 = ra3 = rb0 = rb1 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (more) {
-            const int tap = nx / cchunks, c0 = (nx - tap * cchunks) * CV_KC;
-            const int dy = taps == 9 ? tap / 3 - 1 : 0, dx = taps == 9 ? tap % 3 - 1 : 0;
-            // (py + dy, px + dx) inside the image: then pixel m + dy w + dx is that neighbour, in the same image
-            const float* src = in + ((long long)m0 + (t >> 3) + dy * w + dx) * cin + c0 + 4 * q;
-            const long long step = 32LL * cin;
-            if (pv[0] && (unsigned)(py[0] + dy) < (unsigned)h && (unsigned)(px[0] + dx) < (unsigned)w) ra0 = *(const float4*)(src);
-            if (pv[1] && (unsigned)(py[1] + dy) < (unsigned)h && (unsigned)(px[1] + dx) < (unsigned)w) ra1 = *(const float4*)(src + step);
-            if (pv[2] && (unsigned)(py[2] + dy) < (unsigned)h && (unsigned)(px[2] + dx) < (unsigned)w) ra2 = *(const float4*)(src + 2 * step);
-            if (pv[3] && (unsigned)(py[3] + dy) < (unsigned)h && (unsigned)(px[3] + dx) < (unsigned)w) ra3 = *(const float4*)(src + 3 * step);
-            const float4* wsrc = wpk + ((long long)(2 * by) * groups + nx * (CV_KC / 8)) * 64 + t;
-            rb0 = wsrc[0];
-            rb1 = wsrc[(long long)groups * 64];
-        }
-        if (ch >= 0) {
-#pragma unroll
-            for (int g = 0; g < CV_KC / 8; ++g) {
-                const float4 bv = sB[buf][wn * 256 + g * 64 + lane];
-                float4 av[2];
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-                    av[mt] = *(const float4*)(&sA[buf][(64 * wm + 32 * mt + (lane & 31)) * CV_APITCH + 8 * g + 4 * (lane >> 5)]);
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt].x, bv.x, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt].y, bv.y, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt].z, bv.z, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt].w, bv.w, acc[mt], 0, 0, 0);
-                }
-            }
-        }
-        if (more) {
-            float* dst = &sA[buf ^ 1][(t >> 3) * CV_APITCH + 4 * q];
-            *(float4*)(dst) = ra0;
-            *(float4*)(dst + 32 * CV_APITCH) = ra1;
-            *(float4*)(dst + 64 * CV_APITCH) = ra2;
-            *(float4*)(dst + 96 * CV_APITCH) = ra3;
-            sB[buf ^ 1][t] = rb0;
-            sB[buf ^ 1][256 + t] = rb1;
-        }
-        __syncthreads();
-    }
-    // accumulator register r of lane l: pixel row (r & 3) + 8 (r >> 2) + 4 (l >> 5), channel column l & 31
-    const int n = CV_BN * by + 32 * wn + (lane & 31);
-    const float bn = bias[n];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + 64 * wm + 32 * mt + tile_row(r, lane >> 5);
-            if (m < M) out[(long long)m * cout + n] = fmaxf(acc[mt][r] + bn, 0.f);
-        }
-}
-
-// ---- the pool ----------------------------------------------------------------------------------------------------------------------
-__device__ inline float4 max4(float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
-
-__global__ void __launch_bounds__(256) k_lp_pool(const float* __restrict__ in, int n_img, int h, int w, int c, float* __restrict__ out) {
-    const int ho = h / 2, wo = w / 2, c4 = c / 4;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)n_img * ho * wo * c4;
-    if (i >= total) return;
-    const int cq = (int)(i % c4);
-    const long long p = i / c4;
-    const int x = (int)(p % wo), y = (int)((p / wo) % ho), f = (int)(p / ((long long)wo * ho));
-    const float* s = in + (((long long)f * h + 2 * y) * w + 2 * x) * c + 4 * cq;          // rows 2 y, 2 y + 1 < h; columns 2 x, 2 x + 1 < w
-    const float4 v = max4(max4(*(const float4*)s, *(const float4*)(s + c)), max4(*(const float4*)(s + (long long)w * c), *(const float4*)(s + (long long)w * c + c)));
-    *(float4*)(out + i * 4) = v;
-}
+};
 
 // ---- the head ----------------------------------------------------------------------------------------------------------------------
 // feat [2 F, hw, C]: image f of a at f, of b at F + f.  grid (blocks per image, F) -> partial [F, blocks]
@@ -285,8 +125,6 @@ struct LpShape {
     int head_blocks[LP_TAPS];
 };
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // n_img images through the stack, n_pairs > 0: with the head's partials
 int lp_shape(const char* who, long long n_img, long long n_pairs, long long height, long long width, LpShape& s, size_t& bytes) {
     HN_REQUIRE(n_img >= 1 && height >= LP_MIN_SIDE && width >= LP_MIN_SIDE,
@@ -314,20 +152,12 @@ int lp_shape(const char* who, long long n_img, long long n_pairs, long long heig
     return HN_OK;
 }
 
+// every layer with all nine taps (the first: its one gathered tap) and one split, whatever the size
 int lp_conv(const hn_lpips_model* m, int layer, const float* in, float* out, long long n_img, int h, int w, hipStream_t s) {
-    const int first = layer == 0, cin = first ? CV_KC : LP_CIN[layer], cout = LP_COUT[layer];
-    const long long M = n_img * h * w;
-    k_lp_conv<<<dim3((unsigned)((M + CV_BM - 1) / CV_BM), (unsigned)(cout / CV_BN)), CV_THREADS, 0, s>>>(in, m->wpk[layer], m->bias[layer], out, (int)M, h, w, cin,
-                                                                                                             cout, first ? 1 : 9);
-    HN_LAUNCH_CHECK();
-    return HN_OK;
-}
-
-int lp_pool(const float* in, float* out, long long n_img, int h, int w, int c, hipStream_t s) {
-    const long long total = n_img * (h / 2) * (w / 2) * (c / 4);
-    k_lp_pool<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(in, (int)n_img, h, w, c, out);
-    HN_LAUNCH_CHECK();
-    return HN_OK;
+    const bool first = layer == 0;
+    const int cin = first ? CV_KC : LP_CIN[layer], cout = LP_COUT[layer];
+    return cv_conv<false, false>(in, m->wpk[layer], n_img * h * w, h, w, cin, cout, first, CV_ALL_TAPS, (first ? 1 : 9) * (cin / CV_KC), 1, nullptr,
+                   CvFwd{m->bias[layer], out, cout}, s);
 }
 
 // the five taps of n_a images of `a` followed by n_b of `b`, channel-last, at sh.tap[] of the workspace
@@ -336,23 +166,21 @@ int lp_stack(const hn_lpips_model* m, const unsigned char* a, const unsigned cha
     float *s0 = (float*)(ws + sh.s0), *s1 = (float*)(ws + sh.s1);
     float* tap[LP_TAPS];
     for (int k = 0; k < LP_TAPS; ++k) tap[k] = (float*)(ws + sh.tap[k]);
-    const long long quarters = n * sh.h[0] * sh.w[0] * 8;
-    k_lp_im2col<<<(unsigned)((quarters + 255) / 256), 256, 0, s>>>(a, b, (int)n_a, (int)n, sh.h[0], sh.w[0], s1);
-    HN_LAUNCH_CHECK();
+    HN_TRY_RC(cv_im2col(LpLoad{a, b, (int)n_a, sh.h[0], sh.w[0]}, n, sh.h[0], sh.w[0], s1, s));
     HN_TRY_RC(lp_conv(m, 0, s1, s0, n, sh.h[0], sh.w[0], s));
     HN_TRY_RC(lp_conv(m, 1, s0, tap[0], n, sh.h[0], sh.w[0], s));
-    HN_TRY_RC(lp_pool(tap[0], s1, n, sh.h[0], sh.w[0], 64, s));
+    HN_TRY_RC(cv_pool(tap[0], s1, n, sh.h[0], sh.w[0], 64, s));
     HN_TRY_RC(lp_conv(m, 2, s1, s0, n, sh.h[1], sh.w[1], s));
     HN_TRY_RC(lp_conv(m, 3, s0, tap[1], n, sh.h[1], sh.w[1], s));
-    HN_TRY_RC(lp_pool(tap[1], s1, n, sh.h[1], sh.w[1], 128, s));
+    HN_TRY_RC(cv_pool(tap[1], s1, n, sh.h[1], sh.w[1], 128, s));
     HN_TRY_RC(lp_conv(m, 4, s1, s0, n, sh.h[2], sh.w[2], s));
     HN_TRY_RC(lp_conv(m, 5, s0, s1, n, sh.h[2], sh.w[2], s));
     HN_TRY_RC(lp_conv(m, 6, s1, tap[2], n, sh.h[2], sh.w[2], s));
-    HN_TRY_RC(lp_pool(tap[2], s0, n, sh.h[2], sh.w[2], 256, s));
+    HN_TRY_RC(cv_pool(tap[2], s0, n, sh.h[2], sh.w[2], 256, s));
     HN_TRY_RC(lp_conv(m, 7, s0, s1, n, sh.h[3], sh.w[3], s));
     HN_TRY_RC(lp_conv(m, 8, s1, s0, n, sh.h[3], sh.w[3], s));
     HN_TRY_RC(lp_conv(m, 9, s0, tap[3], n, sh.h[3], sh.w[3], s));
-    HN_TRY_RC(lp_pool(tap[3], s0, n, sh.h[3], sh.w[3], 512, s));
+    HN_TRY_RC(cv_pool(tap[3], s0, n, sh.h[3], sh.w[3], 512, s));
     HN_TRY_RC(lp_conv(m, 10, s0, s1, n, sh.h[4], sh.w[4], s));
     HN_TRY_RC(lp_conv(m, 11, s1, s0, n, sh.h[4], sh.w[4], s));
     HN_TRY_RC(lp_conv(m, 12, s0, tap[4], n, sh.h[4], sh.w[4], s));
@@ -374,7 +202,7 @@ int hn_lpips_create(const float* const* conv_weight, const float* const* conv_bi
     size_t off_w[LP_CONVS], off_b[LP_CONVS], off_l[LP_TAPS], off = 0;
     for (int l = 0; l < LP_CONVS; ++l) {
         off_w[l] = off;
-        off += up256((size_t)LP_COUT[l] * lp_kpad(LP_CIN[l]) * sizeof(float));
+        off += up256(cv_pack_floats(LP_CIN[l], LP_COUT[l], 0) * sizeof(float));
         off_b[l] = off;
         off += up256((size_t)LP_COUT[l] * sizeof(float));
     }
@@ -395,9 +223,7 @@ int hn_lpips_create(const float* const* conv_weight, const float* const* conv_bi
     };
     for (int l = 0; l < LP_CONVS && rc == HN_OK; ++l) {
         float* w = (float*)((char*)blob + off_w[l]);
-        const long long total = (long long)LP_COUT[l] * lp_kpad(LP_CIN[l]);
-        k_lp_pack<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(conv_weight[l], LP_CIN[l], LP_COUT[l], w);
-        fail(hipGetLastError(), "the pack launch");
+        fail(cv_pack(conv_weight[l], LP_CIN[l], LP_COUT[l], 0, w, s), "the pack launch");
         fail(hipMemcpyAsync((char*)blob + off_b[l], conv_bias[l], LP_COUT[l] * sizeof(float), hipMemcpyDeviceToDevice, s), "the bias copy");
         m->wpk[l] = (const float4*)w;
         m->bias[l] = (const float*)((char*)blob + off_b[l]);

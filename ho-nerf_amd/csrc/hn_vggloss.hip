@@ -11,26 +11,24 @@
 // hn_vgg_loss_bwd reads them.  No allocation, no synchronisation, no floating-point atomics: every sum is taken in an order that the
 // shape alone decides, so a repeated call gives the same bits.
 //
-// Precision: exact fp32, v_mfma_f32_32x32x2_f32, for the reason hn_lpips.hip gives.
+// Precision: exact fp32, v_mfma_f32_32x32x2_f32, for the reason hn_conv3x3.h gives.
 //
-// Kernels:
-//   k_vg_pack       [Cout, Cin, 3, 3] -> fragments [N / 32][Kpad / 8][64 lanes] float4, either direction
-//   k_vg_im2col     the first layer's patch gather from the two caller buffers through (y, x, channel) strides -> [2, h, w, 32]
-//   k_vg_conv       the implicit GEMM of hn_lpips.hip's k_lp_conv (128 pixels x 64 channels per workgroup, K in chunks of 32 channels
-//                   of one tap, two LDS buffers) with two additions for the small images this loss sees (21 x 21 -> 21, 10, 5, 2, 1
-//                   pixels per side): blockIdx.z splits the K chunks, each split writing its partial tile, so that a layer of a few
-//                   rows still occupies every CU (vg_splits: as many splits as bring the launch to VG_TARGET_BLOCKS workgroups); and
-//                   taps that lie outside the image for every pixel (a side of 1: only the centre row / column of taps is live) are
-//                   neither loaded nor multiplied.  An unsplit launch runs the epilogue itself.
-//   k_vg_reduce     sums the splits' partials in index order, then the epilogue
-//   the epilogue    VG_FWD: + bias, ReLU.  VG_PLAIN: the value (gradient at a pooled tensor).  VG_GATE: backward-data landing on a
+// The convolution stack (both packings, patch gather, implicit GEMM with its K split and live-tap list, the partials' sum, pool:
+// k_cv_pack, k_cv_im2col, k_cv_conv, k_cv_reduce, k_cv_pool) is hn_conv3x3.h, shared with hn_lpips.hip.  What this file decides for
+// the small images this loss sees (21 x 21 -> 21, 10, 5, 2, 1 pixels per side): the K chunks of a layer of a few rows are split so
+// that it still occupies every CU (vg_splits: as many splits as bring the launch to VG_TARGET_BLOCKS workgroups), and taps that lie
+// outside the image for every pixel (a side of 1: only the centre row / column of taps is live) are left out of the mask.
+//
+// Its own kernels:
+//   VgLoad          the patch gather's loader: the two caller buffers through (y, x, channel) strides -> [2, h, w, 32]
+//   VgEpi           the backward epilogues.  VG_PLAIN: the value (gradient at a pooled tensor).  VG_GATE: backward-data landing on a
 //                   ReLU output y: (+ sign(y_source - y_target) g_loss / numel where y is a tap), times [y > 0].  VG_LAST: the 3
-//                   channels of d loss / d source through the caller's strides.
-//   k_vg_pool       MaxPool2d(2, 2), floor mode;  k_vg_pool_bwd: the gradient to the first maximum of each window in row-major order,
-//                   times [y > 0]
+//                   channels of d loss / d source through the caller's strides.  (Forward is the shared CvFwd: + bias, ReLU.)
+//   k_vg_seed       the gradient at the last tap: VG_GATE on zeros
+//   k_vg_pool_bwd   the gradient to the first maximum of each window in row-major order, times [y > 0]
 //   k_vg_l1         sum |s - t| of one tap's 4096-element slice in fp64 -> one partial; k_vg_l1_final: the partials in index order,
 //                   the five means, their sum
-#include "hn_common.h"
+#include "hn_conv3x3.h"
 
 struct hn_vgg_loss_model {
     void* blob = nullptr;                // one device allocation: both packings, biases
@@ -42,8 +40,6 @@ struct hn_vgg_loss_model {
 namespace hn {
 namespace {
 
-typedef float vg_f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int VG_CONVS = 13, VG_TAPS = 5;
 constexpr int VG_CIN[VG_CONVS] = {3, 64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512};
 constexpr int VG_COUT[VG_CONVS] = {64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512};
@@ -53,21 +49,21 @@ constexpr int VG_MIN_SIDE = 16;
 constexpr long long VG_MAX = 1LL << 31;
 constexpr int VG_TARGET_BLOCKS = 256;                             // the CUs of an MI355X: a launch below this is split over K
 
-constexpr int CV_BM = 128, CV_BN = 64, CV_KC = 32, CV_THREADS = 256;
-constexpr int CV_APITCH = CV_KC + 4;
-constexpr int CV_A_FLOATS = CV_BM * CV_APITCH;
-constexpr int CV_B_FLOAT4 = (CV_BN / 32) * (CV_KC / 8) * 64;
-static_assert(CV_A_FLOATS * 4 * 2 + CV_B_FLOAT4 * 16 * 2 <= 64 * 1024, "static LDS");
-static_assert(CV_BM * (CV_KC / 4) == 4 * CV_THREADS && CV_B_FLOAT4 == 2 * CV_THREADS, "loads per thread and chunk");
-
 constexpr int L1_THREADS = 256, L1_PER_BLOCK = L1_THREADS * 16;
 
-enum { VG_FWD = 0, VG_PLAIN = 1, VG_GATE = 2, VG_LAST = 3 };
+// ---- the first layer's patches -------------------------------------------------------------------------------------------------------
+struct VgLoad {
+    const float *src, *tgt;              // image 0, image 1
+    long long sy, sx, sc;
+    __device__ float operator()(int f, int yy, int xx, int c) const { return (f == 0 ? src : tgt)[yy * sy + xx * sx + c * sc]; }
+};
+
+// ---- the backward epilogues ------------------------------------------------------------------------------------------------------------
+enum { VG_PLAIN, VG_GATE, VG_LAST };
 
 struct VgEpi {
     int mode = VG_PLAIN;
     int n_real = 0;                      // channels of `out` (and of ys, yt): its row pitch
-    const float* bias = nullptr;         // VG_FWD
     const float* ys = nullptr;           // VG_GATE: the source's ReLU output this gradient lands on, [M, n_real]
     const float* yt = nullptr;           // VG_GATE where that output is a tap: the target's; else NULL
     const float* g_loss = nullptr;       // device scalar
@@ -75,227 +71,33 @@ struct VgEpi {
     float* out = nullptr;
     int w = 1;                           // VG_LAST: pixel m = y w + x -> out[y sy + x sx + n sc]
     long long sy = 0, sx = 0, sc = 0;
+
+    __device__ void operator()(int m, int n, float v) const {
+        const long long i = (long long)m * n_real + n;
+        if (mode == VG_PLAIN) {
+            out[i] = v;
+        } else if (mode == VG_GATE) {
+            const float y = ys[i];
+            if (yt != nullptr) {
+                const float d = y - yt[i];
+                v += (float)((d > 0.f) - (d < 0.f)) * (*g_loss * inv_numel);
+            }
+            out[i] = y > 0.f ? v : 0.f;
+        } else if (n < n_real) {
+            const int y = m / w, x = m - y * w;
+            out[y * sy + x * sx + n * sc] = v;
+        }
+    }
 };
-
-__device__ inline void vg_store(const VgEpi& e, int m, int n, float v) {
-    const long long i = (long long)m * e.n_real + n;
-    if (e.mode == VG_FWD) {
-        e.out[i] = fmaxf(v + e.bias[n], 0.f);
-    } else if (e.mode == VG_PLAIN) {
-        e.out[i] = v;
-    } else if (e.mode == VG_GATE) {
-        const float y = e.ys[i];
-        if (e.yt != nullptr) {
-            const float d = y - e.yt[i];
-            v += (float)((d > 0.f) - (d < 0.f)) * (*e.g_loss * e.inv_numel);
-        }
-        e.out[i] = y > 0.f ? v : 0.f;
-    } else if (n < e.n_real) {
-        const int y = m / e.w, x = m - y * e.w;
-        e.out[y * e.sy + x * e.sx + n * e.sc] = v;
-    }
-}
-
-__host__ __device__ inline int vg_kpad(int k_channels) { return (9 * k_channels + CV_KC - 1) / CV_KC * CV_KC; }
-__host__ __device__ inline int vg_npad(int n) { return (n + CV_BN - 1) / CV_BN * CV_BN; }
-
-// ---- weights -----------------------------------------------------------------------------------------------------------------------
-// forward:  N = cout, k = tap cin + c        -> w[n, c, tap]
-// backward: N = cin (padded to 64), k = tap cout + o -> w[o, n, 8 - tap]: d x[q, n] = sum_{tap, o} g[q + d(tap), o] w[o, n, 8 - tap]
-__global__ void __launch_bounds__(256) k_vg_pack(const float* __restrict__ w, int cin, int cout, int bwd, float* __restrict__ out) {
-    const int kc = bwd ? cout : cin, n_rows = bwd ? vg_npad(cin) : cout;
-    const int kpad = vg_kpad(kc), groups = kpad / 8;
-    const long long total = (long long)n_rows * kpad;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int j = (int)(i & 3), lane = (int)((i >> 2) & 63);
-    const long long fg = i >> 8;                                   // nt * groups + g
-    const int g = (int)(fg % groups), nt = (int)(fg / groups);
-    const int n = 32 * nt + (lane & 31), k = 8 * g + 4 * (lane >> 5) + j;
-    float v = 0.f;
-    if (k < 9 * kc) {
-        const int tap = k / kc, c = k - tap * kc;
-        if (!bwd)
-            v = w[((long long)n * cin + c) * 9 + tap];
-        else if (n < cin)
-            v = w[((long long)c * cin + n) * 9 + (8 - tap)];
-    }
-    out[i] = v;
-}
-
-// ---- the first layer's patches -------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_vg_im2col(const float* __restrict__ src, const float* __restrict__ tgt, int h, int w, long long sy, long long sx,
-                                                   long long sc, float* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // (pixel m, quarter q): k = 4 q .. 4 q + 3
-    const long long M = 2LL * h * w;
-    if (i >= M * 8) return;
-    const long long m = i >> 3;
-    const int q = (int)(i & 7);
-    const int f = (int)(m / ((long long)h * w));
-    const int rem = (int)(m - (long long)f * h * w), y = rem / w, x = rem - y * w;
-    const float* img = f == 0 ? src : tgt;
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int k = 4 * q + j;
-        v[j] = 0.f;
-        if (k < 27) {
-            const int tap = k / 3, c = k - 3 * tap, yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
-            if (yy >= 0 && yy < h && xx >= 0 && xx < w) v[j] = img[yy * sy + xx * sx + c * sc];
-        }
-    }
-    *(float4*)(out + i * 4) = make_float4(v[0], v[1], v[2], v[3]);
-}
-
-// ---- the convolution ---------------------------------------------------------------------------------------------------------------
-// the j-th live tap of the mask (bit 3 (dy + 1) + (dx + 1))
-__device__ inline int vg_live_tap(int mask, int j) {
-    int tap = 0;
-#pragma unroll
-    for (int b = 0; b < 9; ++b)
-        if ((mask >> b) & 1) {
-            if (j == 0) tap = b;
-            --j;
-        }
-    return tap;
-}
-
-// in [n_img, h, w, cin] (cin a multiple of 32; M = n_img h w rows).  single: the pixel itself against a one-tap packing (the first
-// layer on its gathered patches); else 3 x 3 with zero padding 1 over the live taps of `tapmask`, n_chunks = live taps x cin / 32.
-// grid (M tiles, N / 64, splits).
-__global__ void __launch_bounds__(CV_THREADS) k_vg_conv(const float* __restrict__ in, const float4* __restrict__ wpk, int M, int h, int w, int cin, int tapmask,
-                                                        int single, int n_chunks, float* __restrict__ partial, VgEpi epi) {
-    __shared__ __attribute__((aligned(16))) float sA[2][CV_A_FLOATS];
-    __shared__ float4 sB[2][CV_B_FLOAT4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
-    const int m0 = blockIdx.x * CV_BM, by = blockIdx.y, bz = blockIdx.z, splits = gridDim.z;
-    const int cchunks = cin / CV_KC, groups = (single ? 1 : 9) * cchunks * (CV_KC / 8);
-    const int c_lo = (int)((long long)bz * n_chunks / splits), c_hi = (int)((long long)(bz + 1) * n_chunks / splits);
-    const int q = t & 7;
-    int py[4], px[4];
-    bool pv[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + (t >> 3) + 32 * i;
-        pv[i] = m < M;
-        const int rem = pv[i] ? m % (h * w) : 0;
-        py[i] = rem / w;
-        px[i] = rem - py[i] * w;
-    }
-    vg_f32x16 acc[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
-    // step ch: fetch chunk ch + 1 into registers, run chunk ch from LDS buffer ch & 1, park the registers in the other buffer, barrier
-    for (int ch = c_lo - 1; ch < c_hi; ++ch) {
-        const int buf = ch & 1, nx = ch + 1;
-        const bool more = nx < c_hi;
-        float4 ra0, ra1, ra2, ra3, rb0, rb1;
-        ra0 = ra1 = ra2 = ra3 = rb0 = rb1 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (more) {
-            const int lt = nx / cchunks, cc = nx - lt * cchunks, c0 = cc * CV_KC;
-            const int tap = single ? 4 : vg_live_tap(tapmask, lt);
-            const int dy = tap / 3 - 1, dx = tap % 3 - 1;
-            const int wchunk = single ? nx : tap * cchunks + cc;
-            // (py + dy, px + dx) inside the image: then pixel m + dy w + dx is that neighbour, in the same image
-            const float* src = in + ((long long)m0 + (t >> 3) + dy * w + dx) * cin + c0 + 4 * q;
-            const long long step = 32LL * cin;
-            if (pv[0] && (unsigned)(py[0] + dy) < (unsigned)h && (unsigned)(px[0] + dx) < (unsigned)w) ra0 = *(const float4*)(src);
-            if (pv[1] && (unsigned)(py[1] + dy) < (unsigned)h && (unsigned)(px[1] + dx) < (unsigned)w) ra1 = *(const float4*)(src + step);
-            if (pv[2] && (unsigned)(py[2] + dy) < (unsigned)h && (unsigned)(px[2] + dx) < (unsigned)w) ra2 = *(const float4*)(src + 2 * step);
-            if (pv[3] && (unsigned)(py[3] + dy) < (unsigned)h && (unsigned)(px[3] + dx) < (unsigned)w) ra3 = *(const float4*)(src + 3 * step);
-            const float4* wsrc = wpk + ((long long)(2 * by) * groups + wchunk * (CV_KC / 8)) * 64 + t;
-            rb0 = wsrc[0];
-            rb1 = wsrc[(long long)groups * 64];
-        }
-        if (ch >= c_lo) {
-#pragma unroll
-            for (int g = 0; g < CV_KC / 8; ++g) {
-                const float4 bv = sB[buf][wn * 256 + g * 64 + lane];
-                float4 av[2];
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-                    av[mt] = *(const float4*)(&sA[buf][(64 * wm + 32 * mt + (lane & 31)) * CV_APITCH + 8 * g + 4 * (lane >> 5)]);
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt].x, bv.x, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt].y, bv.y, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt].z, bv.z, acc[mt], 0, 0, 0);
-                    acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mt].w, bv.w, acc[mt], 0, 0, 0);
-                }
-            }
-        }
-        if (more) {
-            float* dst = &sA[buf ^ 1][(t >> 3) * CV_APITCH + 4 * q];
-            *(float4*)(dst) = ra0;
-            *(float4*)(dst + 32 * CV_APITCH) = ra1;
-            *(float4*)(dst + 64 * CV_APITCH) = ra2;
-            *(float4*)(dst + 96 * CV_APITCH) = ra3;
-            sB[buf ^ 1][t] = rb0;
-            sB[buf ^ 1][256 + t] = rb1;
-        }
-        __syncthreads();
-    }
-    // accumulator register r of lane l: pixel row (r & 3) + 8 (r >> 2) + 4 (l >> 5), channel column l & 31
-    const int n = CV_BN * by + 32 * wn + (lane & 31), npad = CV_BN * gridDim.y;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + 64 * wm + 32 * mt + tile_row(r, lane >> 5);
-            if (m < M) {
-                if (splits == 1)
-                    vg_store(epi, m, n, acc[mt][r]);
-                else
-                    partial[((long long)bz * M + m) * npad + n] = acc[mt][r];
-            }
-        }
-}
-
-// partial [splits, M, npad]: the sum over the splits in index order, then the epilogue
-__global__ void __launch_bounds__(256) k_vg_reduce(const float* __restrict__ partial, int M, int npad, int splits, VgEpi epi) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x, n4 = npad / 4;
-    if (i >= (long long)M * n4) return;
-    const int m = (int)(i / n4), n = 4 * (int)(i - (long long)m * n4);
-    const long long slab = (long long)M * npad;
-    const float* p = partial + (long long)m * npad + n;
-    float4 s = *(const float4*)p;
-    for (int k = 1; k < splits; ++k) {
-        const float4 v = *(const float4*)(p + k * slab);
-        s.x += v.x;
-        s.y += v.y;
-        s.z += v.z;
-        s.w += v.w;
-    }
-    vg_store(epi, m, n, s.x);
-    vg_store(epi, m, n + 1, s.y);
-    vg_store(epi, m, n + 2, s.z);
-    vg_store(epi, m, n + 3, s.w);
-}
 
 // the gradient at the last tap: the epilogue on zeros
 __global__ void __launch_bounds__(256) k_vg_seed(long long total, VgEpi epi) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
-    vg_store(epi, (int)(i / epi.n_real), (int)(i % epi.n_real), 0.f);
+    epi((int)(i / epi.n_real), (int)(i % epi.n_real), 0.f);
 }
 
-// ---- the pool ----------------------------------------------------------------------------------------------------------------------
-__device__ inline float4 max4(float4 a, float4 b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w)); }
-
-__global__ void __launch_bounds__(256) k_vg_pool(const float* __restrict__ in, int n_img, int h, int w, int c, float* __restrict__ out) {
-    const int ho = h / 2, wo = w / 2, c4 = c / 4;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x, total = (long long)n_img * ho * wo * c4;
-    if (i >= total) return;
-    const int cq = (int)(i % c4);
-    const long long p = i / c4;
-    const int x = (int)(p % wo), y = (int)((p / wo) % ho), f = (int)(p / ((long long)wo * ho));
-    const float* s = in + (((long long)f * h + 2 * y) * w + 2 * x) * c + 4 * cq;          // rows 2 y, 2 y + 1 < h; columns 2 x, 2 x + 1 < w
-    const float4 v = max4(max4(*(const float4*)s, *(const float4*)(s + c)), max4(*(const float4*)(s + (long long)w * c), *(const float4*)(s + (long long)w * c + c)));
-    *(float4*)(out + i * 4) = v;
-}
-
+// ---- the pool, backward ---------------------------------------------------------------------------------------------------------------
 // y [h, w, c] (>= 0: ReLU outputs), dp [h / 2, w / 2, c] -> g [h, w, c]: dp at the first maximum of each window (row-major order), where
 // that maximum is positive; 0 elsewhere and in the row / column an odd size leaves outside every window
 __global__ void __launch_bounds__(256) k_vg_pool_bwd(const float* __restrict__ y, const float* __restrict__ dp, int h, int w, int c, float* __restrict__ g) {
@@ -378,8 +180,6 @@ struct VgShape {
     int l1_blocks;
 };
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline int vg_tapmask(int h, int w) {
     int mask = 0;
     for (int tap = 0; tap < 9; ++tap)
@@ -424,7 +224,7 @@ int vg_shape(const char* who, long long height, long long width, VgShape& s, siz
         const int kf = l == 0 ? CV_KC : VG_CIN[l];
         const int sf = vg_splits(2 * (long long)hw, VG_COUT[l], live * kf / CV_KC);
         if (sf > 1 && (size_t)sf * 2 * hw * VG_COUT[l] > part) part = (size_t)sf * 2 * hw * VG_COUT[l];
-        const int nb = vg_npad(VG_CIN[l]);
+        const int nb = cv_npad(VG_CIN[l]);
         const int sb = vg_splits((long long)hw, nb, vg_live_taps(s.h[lv], s.w[lv]) * VG_COUT[l] / CV_KC);
         if (sb > 1 && (size_t)sb * hw * nb > part) part = (size_t)sb * hw * nb;
     }
@@ -443,19 +243,11 @@ int vg_shape(const char* who, long long height, long long width, VgShape& s, siz
     return HN_OK;
 }
 
-// one convolution, either direction: in [M = n_img h w, kc] against the packing wpk of npad rows
-int vg_conv(const float* in, const float4* wpk, long long M, int h, int w, int kc, int npad, bool single, float* partial, const VgEpi& epi, hipStream_t s) {
+// one convolution, either direction: in [M = n_img h w, kc] against the packing wpk of npad rows, live taps only, split by vg_splits
+template <class Epi>
+int vg_conv(const float* in, const float4* wpk, long long M, int h, int w, int kc, int npad, bool single, float* partial, const Epi& epi, hipStream_t s) {
     const int n_chunks = (single ? 1 : vg_live_taps(h, w)) * (kc / CV_KC);
-    const int splits = vg_splits(M, npad, n_chunks);
-    k_vg_conv<<<dim3((unsigned)((M + CV_BM - 1) / CV_BM), (unsigned)(npad / CV_BN), (unsigned)splits), CV_THREADS, 0, s>>>(in, wpk, (int)M, h, w, kc, vg_tapmask(h, w),
-                                                                                                                           single ? 1 : 0, n_chunks, partial, epi);
-    HN_LAUNCH_CHECK();
-    if (splits > 1) {
-        const long long total = M * (npad / 4);
-        k_vg_reduce<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(partial, (int)M, npad, splits, epi);
-        HN_LAUNCH_CHECK();
-    }
-    return HN_OK;
+    return cv_conv<true, true>(in, wpk, M, h, w, kc, npad, single, vg_tapmask(h, w), n_chunks, vg_splits(M, npad, n_chunks), partial, epi, s);
 }
 
 int vg_check_strides(const char* who, long long h, long long w, long long sy, long long sx, long long sc) {
@@ -479,9 +271,9 @@ int hn_vgg_loss_create(const float* const* conv_weight, const float* const* conv
     size_t off_f[VG_CONVS], off_r[VG_CONVS], off_b[VG_CONVS], off = 0;
     for (int l = 0; l < VG_CONVS; ++l) {
         off_f[l] = off;
-        off += up256((size_t)VG_COUT[l] * vg_kpad(VG_CIN[l]) * sizeof(float));
+        off += up256(cv_pack_floats(VG_CIN[l], VG_COUT[l], 0) * sizeof(float));
         off_r[l] = off;
-        off += up256((size_t)vg_npad(VG_CIN[l]) * vg_kpad(VG_COUT[l]) * sizeof(float));
+        off += up256(cv_pack_floats(VG_CIN[l], VG_COUT[l], 1) * sizeof(float));
         off_b[l] = off;
         off += up256((size_t)VG_COUT[l] * sizeof(float));
     }
@@ -499,11 +291,8 @@ int hn_vgg_loss_create(const float* const* conv_weight, const float* const* conv
     for (int l = 0; l < VG_CONVS && rc == HN_OK; ++l) {
         float* wf = (float*)((char*)blob + off_f[l]);
         float* wr = (float*)((char*)blob + off_r[l]);
-        const long long total_f = (long long)VG_COUT[l] * vg_kpad(VG_CIN[l]), total_r = (long long)vg_npad(VG_CIN[l]) * vg_kpad(VG_COUT[l]);
-        k_vg_pack<<<(unsigned)((total_f + 255) / 256), 256, 0, s>>>(conv_weight[l], VG_CIN[l], VG_COUT[l], 0, wf);
-        fail(hipGetLastError(), "the forward pack launch");
-        k_vg_pack<<<(unsigned)((total_r + 255) / 256), 256, 0, s>>>(conv_weight[l], VG_CIN[l], VG_COUT[l], 1, wr);
-        fail(hipGetLastError(), "the backward pack launch");
+        fail(cv_pack(conv_weight[l], VG_CIN[l], VG_COUT[l], 0, wf, s), "the forward pack launch");
+        fail(cv_pack(conv_weight[l], VG_CIN[l], VG_COUT[l], 1, wr, s), "the backward pack launch");
         fail(hipMemcpyAsync((char*)blob + off_b[l], conv_bias[l], VG_COUT[l] * sizeof(float), hipMemcpyDeviceToDevice, s), "the bias copy");
         m->wf[l] = (const float4*)wf;
         m->wb[l] = (const float4*)wr;
@@ -545,24 +334,16 @@ int hn_vgg_loss_fwd(const hn_vgg_loss_model* model, const float* source, const f
     char* ws = (char*)workspace;
     float* partial = (float*)(ws + sh.partial);
     float* col = (float*)(ws + sh.col);
-    const long long quarters = 2LL * sh.h[0] * sh.w[0] * 8;
-    k_vg_im2col<<<(unsigned)((quarters + 255) / 256), 256, 0, s>>>(source, target, sh.h[0], sh.w[0], stride_y, stride_x, stride_c, col);
-    HN_LAUNCH_CHECK();
+    HN_TRY_RC(cv_im2col(VgLoad{source, target, stride_y, stride_x, stride_c}, 2, sh.h[0], sh.w[0], col, s));
     const float* x = col;
     for (int l = 0; l < VG_CONVS; ++l) {
         const int lv = VG_LEVEL[l], h = sh.h[lv], w = sh.w[lv];
         if (l > 0 && VG_LEVEL[l - 1] != lv) {
             float* pooled = (float*)(ws + sh.pool[lv - 1]);
-            const long long total = 2LL * h * w * (VG_CIN[l] / 4);
-            k_vg_pool<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(x, 2, sh.h[lv - 1], sh.w[lv - 1], VG_CIN[l], pooled);
-            HN_LAUNCH_CHECK();
+            HN_TRY_RC(cv_pool(x, pooled, 2, sh.h[lv - 1], sh.w[lv - 1], VG_CIN[l], s));
             x = pooled;
         }
-        VgEpi e;
-        e.mode = VG_FWD;
-        e.n_real = VG_COUT[l];
-        e.bias = model->bias[l];
-        e.out = (float*)(ws + sh.y[l]);
+        const CvFwd e{model->bias[l], (float*)(ws + sh.y[l]), VG_COUT[l]};
         HN_TRY_RC(vg_conv(x, model->wf[l], 2LL * h * w, h, w, l == 0 ? CV_KC : VG_CIN[l], VG_COUT[l], l == 0, partial, e, s));
         x = e.out;
     }
@@ -644,7 +425,7 @@ int hn_vgg_loss_bwd(const hn_vgg_loss_model* model, long long height, long long 
     e.sy = stride_y;
     e.sx = stride_x;
     e.sc = stride_c;
-    HN_TRY_RC(vg_conv(cur, model->wb[0], (long long)sh.h[0] * sh.w[0], sh.h[0], sh.w[0], VG_COUT[0], vg_npad(VG_CIN[0]), false, partial, e, s));
+    HN_TRY_RC(vg_conv(cur, model->wb[0], (long long)sh.h[0] * sh.w[0], sh.h[0], sh.w[0], VG_COUT[0], cv_npad(VG_CIN[0]), false, partial, e, s));
     return HN_OK;
 }
 

@@ -185,24 +185,11 @@ def lpips_vgg_tensors(backbone_state, lin_state=None):
     weights [1, C, 1, 1]) as they lie in the dicts.  Touches no device.  ValueError names every missing or mis-shaped key."""
     lin_state = backbone_state if lin_state is None else lin_state
     bad, conv_w, conv_b, lin_w = [], [], [], []
-
-    def take(state, names, shape, into):
-        found = [n for n in names if n in state]
-        if not found:
-            bad.append('%s: missing' % ' | '.join(names))
-            return
-        v = state[found[0]]
-        v = torch.from_numpy(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
-        if tuple(v.shape) != shape:
-            bad.append('%s: shape %s, expected %s' % (found[0], tuple(v.shape), shape))
-            return
-        into.append(v)
-
     for i, cin, cout in zip(VGG_CONV_INDEX, VGG_CONV_CIN, VGG_CONV_COUT):
-        take(backbone_state, _backbone_names(i, 'weight'), (cout, cin, 3, 3), conv_w)
-        take(backbone_state, _backbone_names(i, 'bias'), (cout,), conv_b)
+        _lib.pick_tensor(backbone_state, _backbone_names(i, 'weight'), (cout, cin, 3, 3), conv_w, bad)
+        _lib.pick_tensor(backbone_state, _backbone_names(i, 'bias'), (cout,), conv_b, bad)
     for k, c in enumerate(LPIPS_TAP_CHANNELS):
-        take(lin_state, ('lin%d.model.1.weight' % k,), (1, c, 1, 1), lin_w)
+        _lib.pick_tensor(lin_state, ('lin%d.model.1.weight' % k,), (1, c, 1, 1), lin_w, bad)
     if bad:
         raise ValueError('LpipsVgg: ' + '; '.join(bad))
     return conv_w, conv_b, lin_w

@@ -256,3 +256,19 @@ def f32(t, device=None):
     """Contiguous fp32 device tensor view/copy of t."""
     t = t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
     return t.detach().to(device=device or 'cuda', dtype=torch.float32).contiguous()
+
+
+def pick_tensor(state, names, shape, into, bad):
+    """Appends to `into` the tensor (or numpy array, as a tensor) that `state` holds under the first of `names` it has, as it lies there,
+    if its shape is `shape`; else appends to `bad` which key is missing or mis-shaped.  Touches no device."""
+    import numpy as np
+    found = [n for n in names if n in state]
+    if not found:
+        bad.append('%s: missing' % ' | '.join(names))
+        return
+    v = state[found[0]]
+    v = torch.from_numpy(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
+    if tuple(v.shape) != shape:
+        bad.append('%s: shape %s, expected %s' % (found[0], tuple(v.shape), shape))
+        return
+    into.append(v)

@@ -557,22 +557,11 @@ def vgg19_tensors(state, channels=VGG19_CONV_COUT):
     `features.<i>.weight | bias` (torchvision's vgg19().state_dict()) or `<i>.weight | bias` (its .features).  Every other key (the
     convolutions 30, 32, 34, the classifier) is ignored.  `channels`: the output channels of the 13 convolutions (a narrower network
     in the tests).  Touches no device.  ValueError names every missing or mis-shaped key."""
-    import numpy as np
     bad, conv_w, conv_b = [], [], []
     cin = (3,) + tuple(channels[:-1])
     for i, ci, co in zip(VGG19_CONV_INDEX, cin, channels):
         for leaf, shape, into in (('weight', (co, ci, 3, 3), conv_w), ('bias', (co,), conv_b)):
-            names = ('features.%d.%s' % (i, leaf), '%d.%s' % (i, leaf))
-            found = [n for n in names if n in state]
-            if not found:
-                bad.append('%s: missing' % ' | '.join(names))
-                continue
-            v = state[found[0]]
-            v = torch.from_numpy(np.asarray(v)) if not isinstance(v, torch.Tensor) else v
-            if tuple(v.shape) != shape:
-                bad.append('%s: shape %s, expected %s' % (found[0], tuple(v.shape), shape))
-                continue
-            into.append(v)
+            _lib.pick_tensor(state, ('features.%d.%s' % (i, leaf), '%d.%s' % (i, leaf)), shape, into, bad)
     if bad:
         raise ValueError('VggLoss: ' + '; '.join(bad))
     return conv_w, conv_b

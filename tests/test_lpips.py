@@ -1,4 +1,4 @@
-"""The device LPIPS (hn_lpips.hip through honerf_amd.image_metrics.LpipsVgg) against the torch restatement of tests/test_lpips_cpu.py
+"""The device LPIPS (hn_lpips.hip + hn_conv3x3.h through honerf_amd.image_metrics.LpipsVgg) against the torch restatement of tests/test_lpips_cpu.py
 on seeded random weights: every element of every tap, every tap mean and every total under helpers.assert_parity (1e-4 of the
 largest float32 reference value; where the float32 reference is itself further from float64, no further from float64 than 1.5 x
 the reference); a dead first tap and a first tap beyond f16's range; exact zeros and symmetry; the same bits on a repeated call,

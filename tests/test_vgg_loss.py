@@ -1,4 +1,4 @@
-"""The device VGG19 perceptual loss (hn_vggloss.hip through honerf_amd.training.VggLoss) against the torch restatement of
+"""The device VGG19 perceptual loss (hn_vggloss.hip + hn_conv3x3.h through honerf_amd.training.VggLoss) against the torch restatement of
 tests/test_vgg_loss_cpu.py on full-width seeded weights and inputs without a marginal gate: loss, the five tap means and
 d loss / d color_fine under helpers.assert_parity at 16 x 16, 21 x 21, 18 x 23 and 33 x 16 (all reach the few-row split-K layers; the
 last two catch a transposed layout), the gradient's structure, a dead relu1_2, determinism, refusals through the raw ABI, and a

@@ -1,4 +1,4 @@
-"""Times of the device LPIPS (hn_lpips.hip through honerf_amd.image_metrics.LpipsVgg) on `--pairs` pairs of `--height` x `--width`
+"""Times of the device LPIPS (hn_lpips.hip + hn_conv3x3.h through honerf_amd.image_metrics.LpipsVgg) on `--pairs` pairs of `--height` x `--width`
 images, 2 of 334 x 512 by default (the size of a harness.render_views leg), against the same arithmetic written with torch operators
 on the device (F.conv2d, F.max_pool2d: what lpips.LPIPS runs), alternating in one process.  The weights are seeded random numbers
 (randn sqrt(2 / (9 Cin)), biases 0.1 randn, linear weights rand / C): the times do not depend on their values.  The HIP path exists

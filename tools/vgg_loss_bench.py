@@ -1,4 +1,4 @@
-"""Times of the device VGG19 perceptual loss (hn_vggloss.hip through honerf_amd.training.VggLoss), forward + backward on one
+"""Times of the device VGG19 perceptual loss (hn_vggloss.hip + hn_conv3x3.h through honerf_amd.training.VggLoss), forward + backward on one
 `--side` x `--side` patch (21: the confs' 441 rays), against the same loss written with torch operators in float32 on the device
 (`training.vgg_loss_reference`: F.conv2d, F.max_pool2d, F.l1_loss and autograd -- the path a user had through `extra_loss` before),
 alternating in one process; and of `training.train_step` on the object nets at side^2 rays with no extra loss, with the torch term and
