@@ -136,6 +136,54 @@ def render_view_buffers(renderer, cameras, H, W, near, far, bt_inv, T_pose_21, R
     return out
 
 
+def render_mesh_buffers(meshes, cameras, H, W, near, far):
+    """`render_view_buffers` for triangle meshes: the same cameras and the same rays (`image_rays`), cast at the meshes by
+    `meshcast.MeshCaster`.  `meshes`: one (vertices, triangles) pair, a list of them, or a MeshCaster (prepared once,
+    for several calls).  Returns device tensors:
+      depth  float32 [V, H, W]     t along the ray of the nearest triangle with near <= t <= far; 0 where there is none
+      normal uint8 [V, H, W, 3]    that triangle's own unit normal in the CAMERA frame, render_view_buffers' encoding exactly: n_world @ R,
+                                   normalised, (n * 0.5 + 0.5) * 255 clamped and truncated; 0 where nothing is hit
+      label  uint8 [V, H, W]       0 where nothing is hit, else 1 + the mesh's index in the list: hand, then object gives
+                                   render_view_buffers' labels
+      face   int32 [V, H, W]       the triangle's index in the concatenation of the meshes (MeshCaster.face_offsets); -1"""
+    from .meshcast import MeshCaster
+    device = torch.device('cuda')
+    caster = meshes if isinstance(meshes, MeshCaster) else MeshCaster(meshes)
+    if caster.n_meshes > 254:
+        raise ValueError('render_mesh_buffers: %d meshes, a uint8 label holds 254' % caster.n_meshes)
+    cams = {k: np.asarray(cameras[k], dtype=np.float32) for k in ('R', 'T', 'focal', 'principal')}
+    V = cams['R'].shape[0]
+    if cams['R'].shape != (V, 3, 3) or cams['T'].shape != (V, 3) or cams['focal'].shape != (V, 2) or cams['principal'].shape != (V, 2):
+        raise ValueError('render_mesh_buffers: cameras must hold R [V,3,3], T [V,3], focal [V,2], principal [V,2]')
+    out = {'depth': torch.empty(V, H, W, device=device), 'normal': torch.empty(V, H, W, 3, dtype=torch.uint8, device=device),
+           'label': torch.empty(V, H, W, dtype=torch.uint8, device=device), 'face': torch.empty(V, H, W, dtype=torch.int32, device=device)}
+    with torch.no_grad():
+        for v in range(V):
+            rays_o, rays_d = image_rays({k: a[v:v + 1] for k, a in cams.items()}, H, W, device)
+            R = torch.from_numpy(cams['R'][v]).to(device)
+            c = caster.cast(rays_o, rays_d, near, far)
+            out['depth'][v] = c['t'].view(H, W)
+            n = torch.nn.functional.normalize(c['normal'] @ R, dim=-1)
+            out['normal'][v] = (((n * 0.5 + 0.5) * 255.0).clamp(0, 255).to(torch.uint8) * c['hit'][:, None]).view(H, W, 3)
+            out['label'][v] = (c['mesh'] + 1).to(torch.uint8).view(H, W)
+            out['face'][v] = c['face'].view(H, W)
+    return out
+
+
+def label_iou(a, b, label):
+    """Intersection over union of the pixels `a == label` and `b == label`, per view: a, b [V, H, W] (or [H, W], one view) label images
+    (arrays or tensors; computed where `a` lives, on the device for the outputs of render_view_buffers / render_mesh_buffers) ->
+    float64 [V].  A view in which neither image has the label (an empty union) gives 1.0."""
+    a = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+    b = (b if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b))).to(a.device)
+    if a.shape != b.shape or a.dim() not in (2, 3):
+        raise ValueError('label_iou: label images of %s and %s, expected two of one shape [V, H, W] or [H, W]' % (tuple(a.shape), tuple(b.shape)))
+    ma, mb = (a == label).reshape(a.shape[0] if a.dim() == 3 else 1, -1), (b == label).reshape(a.shape[0] if a.dim() == 3 else 1, -1)
+    inter = (ma & mb).sum(1).to(torch.float64)
+    union = (ma | mb).sum(1).to(torch.float64)
+    return torch.where(union > 0, inter / union.clamp_min(1.0), torch.ones_like(union))
+
+
 # ---- image files: binary PPM by our own code (always there), anything else through PIL when it imports ---------------------------
 def write_image(path, img):
     """uint8 [H, W, 3] (array or tensor) -> a file.  `.ppm`: binary PPM (P6, maxval 255), the channels stored as they are in the array.

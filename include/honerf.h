@@ -818,6 +818,35 @@ int hn_vgg_loss_fwd(const hn_vgg_loss_model* model, const float* source, const f
 int hn_vgg_loss_bwd(const hn_vgg_loss_model* model, long long height, long long width, long long stride_y, long long stride_x, long long stride_c,
                     const float* g_loss, void* workspace, size_t workspace_bytes, float* g_source, hn_stream_t stream);
 
+/* ---- ray casting of triangle meshes (hn_meshcast.hip): per ray the nearest triangle, for the rays hn_ray_gen makes -------------------
+ * The rule (Woop, Benthin and Wald's watertight scheme), for the ray o + t d with d as given and the triangle (a, b, c):
+ *   kz = the axis of the largest |d_i| (lowest index on ties), kx, ky the next two cyclically, swapped when d[kz] < 0;
+ *   Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz];  A = a - o, Ax = A[kx] - Sx A[kz], Ay = A[ky] - Sy A[kz], likewise B, C;
+ *   U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax, plain fp32 products and differences; if one is exactly 0, all three again
+ *   in double from the same fp32 Ax .. Cy, rounded to fp32;  a miss when one is negative while another is positive (back faces hit) or
+ *   det = (U + V) + W is 0;  t = ((U Az + V Bz) + W Cz) / det, Az = Sz A[kz];  a hit needs near <= t <= far.
+ * The nearest hit is the smallest (t, face) pair, face the index in the caller's triangle array: the result depends neither on `order`
+ * nor on the other rays of the call, and is the same bits on every run.  Never hit: a triangle with a vertex that is not finite, with a
+ * vertex index outside [0, n_verts) (never dereferenced) or with (b - a) x (c - a) of squared length 0 or not finite in fp32; a ray
+ * whose d[kz] is 0.  A ray cannot pass between two triangles that share an edge.
+ *   hn_meshcast_workspace_bytes: the workspace of a mesh of n_tris triangles (0 for n_tris outside [0, 2^31 - 64));
+ *   hn_meshcast_prepare: vertices [n_verts, 3] fp32, triangles [n_tris, 3] int64, order [n_tris] int32 (a permutation of the triangles:
+ *     workspace slot s holds triangle order[s]; an entry outside [0, n_tris) leaves its slot empty) -> the workspace: the triangles in
+ *     that order, the bounds of every block of 64 and of every group of 32 blocks.  No atomics;
+ *   hn_meshcast: rays_o, rays_d [n_rays, 3] fp32 against a prepared workspace -> t [n_rays] fp32 (0 where nothing is hit), face [n_rays]
+ *     int32 (-1 where nothing is hit), bary [n_rays, 2] fp32 (the weights of b and c; 0), normal [n_rays, 3] fp32 (the triangle's own
+ *     normalize((b - a) x (c - a)), not turned toward the ray; 0).  Each output may be NULL: it is then not written.  cull != 0 skips the
+ *     groups and blocks whose bounds the ray misses on [near, min(far, nearest so far)]; cull = 0 walks every block; the same bits
+ *     either way.  Every loop's trip count is fixed by n_tris alone.
+ * Nothing allocates or synchronises.  A NULL input, a negative count, n_tris >= 2^31 - 64, n_rays >= 2^31 - 256 or a workspace that is
+ * too small is HN_EINVAL with a message, before anything is launched; n_tris = 0 or n_rays = 0 launches nothing and returns 0 (the
+ * outputs are left as they are). */
+size_t hn_meshcast_workspace_bytes(long long n_tris);
+int hn_meshcast_prepare(const float* vertices, long long n_verts, const long long* triangles, long long n_tris, const int* order, void* workspace,
+                        size_t workspace_bytes, hn_stream_t stream);
+int hn_meshcast(const void* workspace, size_t workspace_bytes, long long n_tris, const float* rays_o, const float* rays_d, long long n_rays, float near,
+                float far, int cull, float* t, int* face, float* bary, float* normal, hn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
