@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "hn_common.h"
+#include "hn_field_launch.h"
 #include "hn_mlp2.h"   // (v2::WG_SAMPLES, v2::XCD_PACE_MIN_ROUNDS: from which size the hand field kernel treats a launch as long)
 
 namespace hn {
@@ -91,25 +92,6 @@ int adam_step(int, float* const*, const float* const*, float* const*, float* con
 int fit_total_bwd(const float*, const float*, const float*, const float*, const float*, int, float*, float*, float*, float*, hipStream_t);
 int fit_loss_grads(const float*, const float*, const float*, const float*, int, const float*, const float*, int, const float*,
                    const float*, float*, float*, float*, float*, hipStream_t);
-size_t field_obj_workspace_bytes(int n_pts, int n_cus);
-size_t field_hand_workspace_bytes(int n_pts, int n_cus);
-int launch_field_obj(const hn_field*, const float*, const float*, int, int, float*, float*, float*, float*, void*, size_t,
-                     bool, hipStream_t);
-int launch_field_hand(const hn_field*, const float*, int, const float*, const float*, int, int, float*, float*, float*,
-                      float*, void*, size_t, bool, hipStream_t);
-
-namespace v2 {
-size_t field2_obj_workspace_bytes(int n_pts, int n_cus);
-int launch_field2_obj(const hn_field*, const float*, const float*, int, int, float*, float*, float*, float*, void*, size_t,
-                      bool, hipStream_t, void* tape, size_t tape_bytes);
-size_t field2_hand_workspace_bytes(int n_pts, int n_cus);
-int launch_field2_hand(const hn_field*, const float*, int, const float*, const float*, int, int, float*, float*, float*,
-                       float*, void*, size_t, bool, hipStream_t, void* tape, size_t tape_bytes);
-size_t field2_obj_tape_bytes(int n_pts);
-size_t field2_hand_tape_bytes(int n_pts);
-int hand_dropped_samples(unsigned long long* n, bool reset);
-}
-
 constexpr int MAX_DEVICES = 64;
 
 __global__ void k_scale(float* v, int n, float s) {
@@ -265,28 +247,6 @@ static int join_from(SideStream* x, hipStream_t s) {
     HN_CHECK_HIP(hipStreamWaitEvent(s, x->join, 0));
     return HN_OK;
 }
-
-static thread_local const int* g_launch_n_pts_dev = nullptr;
-const int* launch_n_pts_dev() { return g_launch_n_pts_dev; }
-void set_launch_n_pts_dev(const int* p) { g_launch_n_pts_dev = p; }
-// (set by the caller around an object adjoint launch: g_rays_d is [n, 3], one row per SAMPLE, stored -- the caller sums the rows of a
-// ray in a fixed order -- instead of [n / spr, 3] accumulated with atomics)
-static thread_local bool g_launch_dir_per_sample = false;
-bool launch_dir_per_sample() { return g_launch_dir_per_sample; }
-void set_launch_dir_per_sample(bool on) { g_launch_dir_per_sample = on; }
-static thread_local bool g_launch_three_pass = false;
-bool launch_three_pass() { return g_launch_three_pass; }
-struct ThreePassScope {   // around a taped render (hn_common.h: launch_three_pass)
-    const bool before;
-    explicit ThreePassScope(bool on) : before(g_launch_three_pass) { g_launch_three_pass = before || on; }
-    ~ThreePassScope() { g_launch_three_pass = before; }
-};
-static thread_local const int* g_launch_orig_idx = nullptr;
-const int* launch_orig_idx() { return g_launch_orig_idx; }
-void set_launch_orig_idx(const int* p) { g_launch_orig_idx = p; }
-static thread_local const int* g_launch_frame_seg = nullptr;
-const int* launch_frame_seg() { return g_launch_frame_seg; }
-void set_launch_frame_seg(const int* p) { g_launch_frame_seg = p; }
 
 // ---- exact far-field skip of the hand field (SURVEY B-11, hn_field_set_compaction) ---------------------------------------
 // A sample whose bone masks h_b = 1 - sigmoid(200 (v_b - cutoff_b)) (utils/fields.py:33-35) are ALL exactly 0 in fp32 sees
@@ -662,6 +622,12 @@ struct CompactRec {
         sdf_c = rgb_c + 3 * (N + 1);
         seg = reinterpret_cast<int*>(sdf_c + (N + 1)) + 16;   // the frame table of the frame-aligned layout (k_hand_compact_write)
     }
+    // the options of a field launch over this record's compact list: its device-side count and its permutation
+    FieldLaunchOpts opts(FieldLaunchOpts lo) const {
+        lo.n_pts_dev = n_dev;
+        lo.orig_idx = idx;
+        return lo;
+    }
     // frames of the frame-aligned layout for these sizes (0: the plain layout)
     static int aligned_frames(int n, int n_frames, int pts_per_frame) {
         return (n_frames > 1 && n_frames <= COMPACT_MAX_FRAMES && pts_per_frame % 128 == 0 && (size_t)n_frames * pts_per_frame == (size_t)n) ? n_frames : 0;
@@ -687,27 +653,6 @@ static int order_hand_live_first(CompactRec& cr, const float* pts, int n, const 
     HN_LAUNCH_CHECK();
     return HN_OK;
 }
-// HONERF_LIVE_FIRST, read per render call: 0 = off; unset or 1 = on for launches the field kernel treats as long; 2 = on at every size
-static int live_first_mode() {
-    const char* e = getenv("HONERF_LIVE_FIRST");
-    if (e == nullptr || e[0] == '\0') return 1;
-    return e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1);
-}
-// HONERF_UNIFORM_STASH, read per hand-field launch (hn_field2_hand.hip, Hand2Args::ustash): 0 = full-width stash traffic in every wave;
-// 2 = a wave whose 32 samples are all far stores and reads ONE column per half, at the addresses its lanes 0 and 32 always used;
-// unset or 1 = the same column packed into whole 128-byte lines of the wave's free slot (the same bits in all three: DESIGN.md 3.1)
-int uniform_stash_mode() {
-    const char* e = getenv("HONERF_UNIFORM_STASH");
-    if (e == nullptr) return 1;
-    return e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1);
-}
-// HONERF_FAR_TILES, read per hand-field launch (hn_field2_hand.hip, Hand2Args::far_tiles): unset or 1 = a sample tile whose four waves
-// are all far runs the all-far tile program of the full evaluation kernels; 0 = every tile runs the general program (the same bits)
-int far_tiles_mode() {
-    const char* e = getenv("HONERF_FAR_TILES");
-    return (e != nullptr && e[0] == '0') ? 0 : 1;
-}
-
 // bump allocator over the caller's workspace
 struct Arena {
     char* base;
@@ -769,11 +714,11 @@ static size_t field_ws(const hn_field* f, int n_pts) {
 }
 
 static int field_sdf(const hn_field* f, const float* pts, int n, const float* bt, const float* Tp, int n_frames, int ppf,
-                     float* sdf, void* ws, size_t ws_bytes, hipStream_t s) {
+                     float* sdf, void* ws, size_t ws_bytes, hipStream_t s, const FieldLaunchOpts& lo) {
     if (f->precision == HN_PREC_F16X3 && f->kind == HN_FIELD_OBJ)
-        return v2::launch_field2_obj(f, pts, nullptr, n, 1, sdf, nullptr, nullptr, nullptr, ws, ws_bytes, false, s, nullptr, 0);
+        return v2::launch_field2_obj(f, pts, nullptr, n, 1, sdf, nullptr, nullptr, nullptr, ws, ws_bytes, false, s, lo);
     if (f->precision == HN_PREC_F16X3)
-        return v2::launch_field2_hand(f, pts, n, bt, Tp, n_frames, ppf, sdf, nullptr, nullptr, nullptr, ws, ws_bytes, false, s, nullptr, 0);
+        return v2::launch_field2_hand(f, pts, n, bt, Tp, n_frames, ppf, sdf, nullptr, nullptr, nullptr, ws, ws_bytes, false, s, lo);
     if (f->kind == HN_FIELD_OBJ) return launch_field_obj(f, pts, nullptr, n, 1, sdf, nullptr, nullptr, nullptr, ws, ws_bytes, false, s);
     return launch_field_hand(f, pts, n, bt, Tp, n_frames, ppf, sdf, nullptr, nullptr, nullptr, ws, ws_bytes, false, s);
 }
@@ -788,17 +733,17 @@ static std::mutex g_field_timer_mutex;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_field_timer_pairs;
 static int field_eval_launch(const hn_field* f, const float* pts, const float* rays_d, int n, int spr, const float* bt,
                              const float* Tp, int n_frames, int ppf, float* sdf, float* grad, float* rgb, float* feat, void* ws,
-                             size_t ws_bytes, hipStream_t s, void* tape, size_t tape_bytes);
+                             size_t ws_bytes, hipStream_t s, const FieldLaunchOpts& lo, void* tape, size_t tape_bytes);
 static int field_eval(const hn_field* f, const float* pts, const float* rays_d, int n, int spr, const float* bt,
                       const float* Tp, int n_frames, int ppf, float* sdf, float* grad, float* rgb, float* feat, void* ws,
-                      size_t ws_bytes, hipStream_t s, void* tape = nullptr, size_t tape_bytes = 0) {
+                      size_t ws_bytes, hipStream_t s, const FieldLaunchOpts& lo, void* tape = nullptr, size_t tape_bytes = 0) {
     if (g_field_timer.load(std::memory_order_relaxed) == 0 || n <= 0)
-        return field_eval_launch(f, pts, rays_d, n, spr, bt, Tp, n_frames, ppf, sdf, grad, rgb, feat, ws, ws_bytes, s, tape, tape_bytes);
+        return field_eval_launch(f, pts, rays_d, n, spr, bt, Tp, n_frames, ppf, sdf, grad, rgb, feat, ws, ws_bytes, s, lo, tape, tape_bytes);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HN_CHECK_HIP(hipEventCreate(&e0));
     HN_CHECK_HIP(hipEventCreate(&e1));
     HN_CHECK_HIP(hipEventRecord(e0, s));
-    const int rc = field_eval_launch(f, pts, rays_d, n, spr, bt, Tp, n_frames, ppf, sdf, grad, rgb, feat, ws, ws_bytes, s, tape, tape_bytes);
+    const int rc = field_eval_launch(f, pts, rays_d, n, spr, bt, Tp, n_frames, ppf, sdf, grad, rgb, feat, ws, ws_bytes, s, lo, tape, tape_bytes);
     HN_CHECK_HIP(hipEventRecord(e1, s));
     std::lock_guard<std::mutex> lk(g_field_timer_mutex);
     g_field_timer_pairs.emplace_back(e0, e1);
@@ -806,11 +751,11 @@ static int field_eval(const hn_field* f, const float* pts, const float* rays_d, 
 }
 static int field_eval_launch(const hn_field* f, const float* pts, const float* rays_d, int n, int spr, const float* bt,
                              const float* Tp, int n_frames, int ppf, float* sdf, float* grad, float* rgb, float* feat, void* ws,
-                             size_t ws_bytes, hipStream_t s, void* tape, size_t tape_bytes) {
+                             size_t ws_bytes, hipStream_t s, const FieldLaunchOpts& lo, void* tape, size_t tape_bytes) {
     if (f->precision == HN_PREC_F16X3 && f->kind == HN_FIELD_OBJ)
-        return v2::launch_field2_obj(f, pts, rays_d, n, spr, sdf, grad, rgb, feat, ws, ws_bytes, true, s, tape, tape_bytes);
+        return v2::launch_field2_obj(f, pts, rays_d, n, spr, sdf, grad, rgb, feat, ws, ws_bytes, true, s, lo, tape, tape_bytes);
     if (f->precision == HN_PREC_F16X3)
-        return v2::launch_field2_hand(f, pts, n, bt, Tp, n_frames, ppf, sdf, grad, rgb, feat, ws, ws_bytes, true, s, tape, tape_bytes);
+        return v2::launch_field2_hand(f, pts, n, bt, Tp, n_frames, ppf, sdf, grad, rgb, feat, ws, ws_bytes, true, s, lo, tape, tape_bytes);
     if (f->kind == HN_FIELD_OBJ) return launch_field_obj(f, pts, rays_d, n, spr, sdf, grad, rgb, feat, ws, ws_bytes, true, s);
     return launch_field_hand(f, pts, n, bt, Tp, n_frames, ppf, sdf, grad, rgb, feat, ws, ws_bytes, true, s);
 }
@@ -925,7 +870,8 @@ static int render_single_impl(const hn_field* f, const float* rays_o, const floa
                               int n_rays, double near, double far, int n_samples, int n_importance, int steps,
                               const float* bt_inv, const float* T_pose, float* color, float* cdf, float* weight_sum,
                               float* weight_max, float* gradient_error, float* z_vals, void* workspace,
-                              size_t workspace_bytes, hipStream_t s, size_t* need, void* keep_block = nullptr, size_t keep_bytes = 0) {
+                              size_t workspace_bytes, hipStream_t s, size_t* need, const FieldLaunchOpts& lo, int live_first,
+                              void* keep_block = nullptr, size_t keep_bytes = 0) {
     HN_REQUIRE(n_samples >= 2 && n_importance >= 0 && n_rays >= 0, "bad sample counts");
     HN_REQUIRE(n_importance == 0 || (steps >= 1 && n_importance % steps == 0), "n_importance must divide into steps");
     const int S = n_samples + n_importance;
@@ -965,16 +911,11 @@ static int render_single_impl(const hn_field* f, const float* rays_o, const floa
     const int cus_now = device_cus() > 0 ? device_cus() : 256;
     auto sdf_pass = [&](const float* p, int n, float* out) -> int {
         if (!(may_compact && hand_compaction(f, 1, (size_t)n) && (size_t)n > (size_t)32 * (size_t)cus_now))
-            return field_sdf(f, p, n, bt_inv, T_pose, 1, n, out, fws, fws_bytes, s);
+            return field_sdf(f, p, n, bt_inv, T_pose, 1, n, out, fws, fws_bytes, s, lo);
         CompactRec cr;
         cr.at(crec_ws, (size_t)n);
         HN_TRY(compact_hand(cr, p, n, bt_inv, T_pose, 1, n, s));
-        set_launch_n_pts_dev(cr.n_dev);
-        set_launch_orig_idx(cr.idx);
-        const int rc = field_sdf(f, cr.pts_c, n + 1, bt_inv, T_pose, 1, n, cr.sdf_c, fws, fws_bytes, s);
-        set_launch_n_pts_dev(nullptr);
-        set_launch_orig_idx(nullptr);
-        HN_TRY(rc);
+        HN_TRY(field_sdf(f, cr.pts_c, n + 1, bt_inv, T_pose, 1, n, cr.sdf_c, fws, fws_bytes, s, cr.opts(lo)));
         hipLaunchKernelGGL(k_hand_scatter_sdf, dim3((n + 255) / 256), dim3(256), 0, s, cr.pos, n, cr.n_dev, cr.sdf_c, out);
         HN_LAUNCH_CHECK();
         return HN_OK;
@@ -1045,21 +986,16 @@ static int render_single_impl(const hn_field* f, const float* rays_o, const floa
         HN_TRY(compact_hand(cr, t.pts, (int)N, bt_inv, T_pose, 1, hand_ppf, s));
         if (keep_block != nullptr) HN_TRY(kept_count_send(keep_block, cr.n_dev, s));
         float *sdf_c = keep_block ? kp.sdf : cr.sdf_c, *grad_c = keep_block ? kp.grad : cr.grad_c, *rgb_c = keep_block ? kp.rgb : cr.rgb_c;
-        set_launch_n_pts_dev(cr.n_dev);
-        set_launch_orig_idx(cr.idx);
-        const int rc = field_eval(f, cr.pts_c, rays_d, (int)N + 1, S, bt_inv, T_pose, 1, hand_ppf, sdf_c, grad_c, rgb_c, keep_block ? kp.feat : nullptr, fws,
-                                  fws_bytes, s, keep_block ? kp.tape : nullptr, keep_block ? kp.tape_bytes : 0);
-        set_launch_n_pts_dev(nullptr);
-        set_launch_orig_idx(nullptr);
-        HN_TRY(rc);
+        HN_TRY(field_eval(f, cr.pts_c, rays_d, (int)N + 1, S, bt_inv, T_pose, 1, hand_ppf, sdf_c, grad_c, rgb_c, keep_block ? kp.feat : nullptr, fws, fws_bytes,
+                          s, cr.opts(lo), keep_block ? kp.tape : nullptr, keep_block ? kp.tape_bytes : 0));
         hipLaunchKernelGGL(k_hand_scatter, dim3(((int)N + 255) / 256), dim3(256), 0, s, cr.pos, (int)N, cr.n_dev, sdf_c, grad_c, rgb_c, sdf, grad, rgb);
         HN_LAUNCH_CHECK();
     } else if (keep_block != nullptr) {
-        HN_TRY(field_eval(f, t.pts, rays_d, (int)N, S, bt_inv, T_pose, 1, hand_ppf, kp.sdf, kp.grad, kp.rgb, kp.feat, fws, fws_bytes, s, kp.tape, kp.tape_bytes));
+        HN_TRY(field_eval(f, t.pts, rays_d, (int)N, S, bt_inv, T_pose, 1, hand_ppf, kp.sdf, kp.grad, kp.rgb, kp.feat, fws, fws_bytes, s, lo, kp.tape, kp.tape_bytes));
         sdf = kp.sdf;
         grad = kp.grad;
         rgb = kp.rgb;
-    } else if (const int lf = may_order ? live_first_mode() : 0;
+    } else if (const int lf = may_order ? live_first : 0;
                lf == 2 || (lf == 1 && (N + v2::WG_SAMPLES - 1) / v2::WG_SAMPLES >= (size_t)v2::XCD_PACE_MIN_ROUNDS * (size_t)cus_now)) {
         // Live-first order: every sample is evaluated, by the same kernel in ONE launch -- on the list
         // [live samples | far samples], each part in dense order -- and the outputs go back to dense order in front of alpha.  No result
@@ -1068,14 +1004,13 @@ static int render_single_impl(const hn_field* f, const float* rays_o, const floa
         CompactRec cr;
         cr.at(crec_ws, N);
         HN_TRY(order_hand_live_first(cr, t.pts, (int)N, bt_inv, T_pose, s));
-        set_launch_orig_idx(cr.idx);
-        const int rc = field_eval(f, cr.pts_c, rays_d, (int)N, S, bt_inv, T_pose, 1, hand_ppf, cr.sdf_c, cr.grad_c, cr.rgb_c, nullptr, fws, fws_bytes, s);
-        set_launch_orig_idx(nullptr);
-        HN_TRY(rc);
+        FieldLaunchOpts ordered = lo;   // (every sample is in the list: no device-side count)
+        ordered.orig_idx = cr.idx;
+        HN_TRY(field_eval(f, cr.pts_c, rays_d, (int)N, S, bt_inv, T_pose, 1, hand_ppf, cr.sdf_c, cr.grad_c, cr.rgb_c, nullptr, fws, fws_bytes, s, ordered));
         hipLaunchKernelGGL(k_hand_scatter, dim3(((int)N + 255) / 256), dim3(256), 0, s, cr.pos, (int)N, cr.n_dev, cr.sdf_c, cr.grad_c, cr.rgb_c, sdf, grad, rgb);
         HN_LAUNCH_CHECK();
     } else {
-        HN_TRY(field_eval(f, t.pts, rays_d, (int)N, S, bt_inv, T_pose, 1, hand_ppf, sdf, grad, rgb, nullptr, fws, fws_bytes, s));
+        HN_TRY(field_eval(f, t.pts, rays_d, (int)N, S, bt_inv, T_pose, 1, hand_ppf, sdf, grad, rgb, nullptr, fws, fws_bytes, s, lo));
     }
     HN_TRY(alpha(sdf, grad, rays_d, dists, (int)N, S, f->inv_s, al, cdf, s, f->inv_s_dev));
     HN_CHECK_HIP(hipMemsetAsync(gradient_error, 0, sizeof(float), s));
@@ -1091,8 +1026,8 @@ static int render_dual_impl(const hn_field* hand, const hn_field* obj, const flo
                             int n_importance, int steps, const float* bt_inv, const float* T_pose, const float* Ro,
                             const float* To, int batch_quirk, float* color, float* weight_sum, float* sdf_hand,
                             float* sdf_obj, float* grad_hand, float* grad_obj, float* gradient_error, float* z_vals,
-                            void* workspace, size_t workspace_bytes, hipStream_t s, size_t* need, size_t* aux_offsets = nullptr,
-                            void* tape = nullptr, size_t tape_bytes = 0, size_t* compact_offsets = nullptr, int flags = 0) {
+                            void* workspace, size_t workspace_bytes, hipStream_t s, size_t* need, const FieldLaunchOpts& lo,
+                            size_t* aux_offsets = nullptr, void* tape = nullptr, size_t tape_bytes = 0, size_t* compact_offsets = nullptr, int flags = 0) {
     const bool ro_t = (flags & HN_DUAL_RO_TRANSPOSED) != 0;        // Ro holds obj_r: its transpose is the rotation to apply
     const bool obj_side = (flags & HN_DUAL_OBJ_POSE_ON_SIDE) != 0;  // Ro / To are produced on the side stream (pipelined fitting step)
     HN_REQUIRE(n_samples >= 2 && n_importance >= 0 && n_frames >= 1 && rpf >= 0, "bad sizes");
@@ -1203,7 +1138,7 @@ static int render_dual_impl(const hn_field* hand, const hn_field* obj, const flo
         const bool coarse_compact = crec_ws != nullptr && hand_compaction(hand, n_frames, (size_t)nc);
         auto obj_coarse = [&]() -> int {
             HN_TRY(sample_points(o_obj, d_obj, to.z_a, n_rays, n_samples, 0, 0.f, to.pts, nullptr, so));
-            return field_sdf(obj, to.pts, nc, bt_inv, T_pose, 1, nc, to.sdf_a, fwso, fws_o, so);
+            return field_sdf(obj, to.pts, nc, bt_inv, T_pose, 1, nc, to.sdf_a, fwso, fws_o, so, lo);
         };
         HN_TRY(sample_points(rays_o, rays_d, th.z_a, n_rays, n_samples, 0, 0.f, th.pts, nullptr, s));
         UpsPre coarse_gather{};
@@ -1214,12 +1149,7 @@ static int render_dual_impl(const hn_field* hand, const hn_field* obj, const flo
             cr.at(crec_ws, (size_t)nc);
             HN_TRY(compact_hand(cr, th.pts, nc, bt_inv, T_pose, n_frames, rpf * n_samples, s));
             if (side != nullptr) HN_TRY(gate_to(side, s));
-            set_launch_n_pts_dev(cr.n_dev);
-            set_launch_orig_idx(cr.idx);
-            const int rc = field_sdf(hand, cr.pts_c, nc + 1, bt_inv, T_pose, n_frames, rpf * n_samples, cr.sdf_c, fwsh, fws_h, s);
-            set_launch_n_pts_dev(nullptr);
-            set_launch_orig_idx(nullptr);
-            HN_TRY(rc);
+            HN_TRY(field_sdf(hand, cr.pts_c, nc + 1, bt_inv, T_pose, n_frames, rpf * n_samples, cr.sdf_c, fwsh, fws_h, s, cr.opts(lo)));
             HN_TRY(obj_coarse());
             if (steps >= 1 && fused_rounds && upsample_fused_ok(n_rays, n_samples, n_new)) {
                 coarse_gather = UpsPre{nullptr, nullptr, 0, 0, nullptr, th.sdf_a, cr.pos, cr.n_dev, cr.sdf_c};   // the first up_sample launch reads through the record
@@ -1229,7 +1159,7 @@ static int render_dual_impl(const hn_field* hand, const hn_field* obj, const flo
             }
         } else {
             HN_TRY(obj_coarse());
-            HN_TRY(field_sdf(hand, th.pts, nc, bt_inv, T_pose, n_frames, rpf * n_samples, th.sdf_a, fwsh, fws_h, s));
+            HN_TRY(field_sdf(hand, th.pts, nc, bt_inv, T_pose, n_frames, rpf * n_samples, th.sdf_a, fwsh, fws_h, s, lo));
         }
         // A round is up_sample -> sdf of the new depths -> cat_z_vals; in the wave form of up_sample (the fitting loops' batch sizes)
         // a round's cat_z_vals runs at the head of the NEXT round's up_sample launch (UpsPre: `pending`), and the hand's coarse sdf row is
@@ -1269,7 +1199,7 @@ static int render_dual_impl(const hn_field* hand, const hn_field* obj, const flo
                 }
                 if (i + 1 < steps) {
                     HN_TRY(field_sdf(r.f, t.pts, n_rays * n_new, bt_inv, T_pose, r.nf, r.which == 0 ? rpf * n_new : n_rays * n_new, t.sdf_new,
-                                     r.fws, r.fwb, r.st));
+                                     r.fws, r.fwb, r.st, lo));
                     if (fused_rounds && upsample_fused_ok(n_rays, r.k + n_new, n_new)) {
                         pending[r.which] = true;
                     } else {
@@ -1328,13 +1258,8 @@ static int render_dual_impl(const hn_field* hand, const hn_field* obj, const flo
         else if (side != nullptr)
             HN_TRY(fork_to(side, s));
         forked = true;
-        set_launch_n_pts_dev(cr.n_dev);
-        set_launch_orig_idx(cr.idx);
-        const int rc = field_eval(hand, cr.pts_c, rays_d, (int)N + 1, S, bt_inv, T_pose, n_frames, rpf * S, cr.sdf_c, cr.grad_c, cr.rgb_c, nullptr, fwsh,
-                                  fws_h, s, in_tape ? tp_h : nullptr, in_tape ? tape_h : 0);
-        set_launch_n_pts_dev(nullptr);
-        set_launch_orig_idx(nullptr);
-        HN_TRY(rc);
+        HN_TRY(field_eval(hand, cr.pts_c, rays_d, (int)N + 1, S, bt_inv, T_pose, n_frames, rpf * S, cr.sdf_c, cr.grad_c, cr.rgb_c, nullptr, fwsh, fws_h, s,
+                          cr.opts(lo), in_tape ? tp_h : nullptr, in_tape ? tape_h : 0));
         hipLaunchKernelGGL(k_hand_scatter, dim3(((int)N + 255) / 256), dim3(256), 0, s, cr.pos, (int)N, cr.n_dev, cr.sdf_c, cr.grad_c, cr.rgb_c, sdf_hand,
                            grad_hand, rgb_h);
         HN_LAUNCH_CHECK();
@@ -1345,14 +1270,14 @@ static int render_dual_impl(const hn_field* hand, const hn_field* obj, const flo
             HN_TRY(fork_to(side, s));
         forked = true;
         HN_TRY(field_eval(hand, pts, rays_d, (int)N, S, bt_inv, T_pose, n_frames, rpf * S, sdf_hand, grad_hand, rgb_h, nullptr,
-                          fwsh, fws_h, s, tp_h, tape_h));
+                          fwsh, fws_h, s, lo, tp_h, tape_h));
     }
     (void)forked;
     HN_TRY(alpha(sdf_hand, grad_hand, rays_d, dists, (int)N, S, hand->inv_s, al_h, nullptr, s));
     if (!obj_rays_made) HN_TRY(obj_local_fwd(rays_o, rays_d, Ro, To, n_frames, rpf, o_obj, d_obj, so, ro_t));
     if (!obj_pts_made) HN_TRY(sample_points(o_obj, d_obj, z_final, n_rays, S, 1, sample_dist, pts_o, dists_o, so));
     HN_TRY(field_eval(obj, pts_o, d_obj, (int)N, S, nullptr, nullptr, 1, (int)N, sdf_obj, grad_obj, rgb_o, nullptr, fwso,
-                      fws_o, so, tp_o, tape_o));
+                      fws_o, so, lo, tp_o, tape_o));
     HN_TRY(alpha(sdf_obj, grad_obj, d_obj, dists_o, (int)N, S, obj->inv_s, al_o, nullptr, so));
     // (on s while it waits for the object branch: off the critical path)
     HN_CHECK_HIP(hipMemsetAsync(gradient_error, 0, 2 * sizeof(float), s));
@@ -1368,15 +1293,6 @@ void pool_free(void* p);
 size_t pool_trim();
 namespace bwd {
 int weight_norm_bwd(const hn_field*, const hn_mlp_desc*, const hn_mlp_desc*, const float*, const hn_mlp_desc*, const hn_mlp_desc*, hipStream_t);
-typedef std::function<int(const float* z8, const float* grad, const float* rgb_pre)> MidHook;
-typedef std::function<int(const float* sdf, const float* grad, const float* rgb)> MidHook2;
-size_t field_bwd_workspace_bytes(const hn_field* f, int n);
-int field_eval_bwd(const hn_field* f, const float* pts, const float* rays_d, int n, int spr, const float* bt_inv,
-                   const float* T_pose, int n_frames, int pts_per_frame, const float* g_sdf, const float* g_grad,
-                   const float* g_rgb, float* g_pts, float* g_rays_d, float* g_bt_inv, float* g_T_pose, void* workspace,
-                   size_t workspace_bytes, hipStream_t s, const void* tape, const float* grad, const float* rgb,
-                   float* g_params = nullptr, const MidHook* mid = nullptr, const MidHook2* mid2 = nullptr, const float* sdf_t = nullptr,
-                   const float* feat_t = nullptr);
 }
 
 // Backward pass of the two-field render (what loss.backward() runs through NeuSRenderer_fitting.render in the fitting
@@ -1390,7 +1306,8 @@ static int render_dual_bwd_impl(const hn_field* hand, const hn_field* obj, const
                                 const float* alpha_o, const float* g_color, const float* g_wsum, const float* g_sdf_h,
                                 const float* g_sdf_o, const float* g_grad_h, const float* g_grad_o, const float* g_eik,
                                 float* g_rays_o, float* g_rays_d, float* g_bt_inv, float* g_T_pose, float* g_Ro, float* g_To,
-                                void* workspace, size_t workspace_bytes, hipStream_t s, size_t* need, const void* tape = nullptr, int flags = 0) {
+                                void* workspace, size_t workspace_bytes, hipStream_t s, size_t* need, const FieldLaunchOpts& lo,
+                                const void* tape = nullptr, int flags = 0) {
     const bool ro_t = (flags & HN_DUAL_RO_TRANSPOSED) != 0;
     const bool no_join = (flags & HN_DUAL_BWD_NO_JOIN) != 0;   // the object branch's results stay on the side stream (pipelined fitting step)
     HN_REQUIRE(hand->kind == HN_FIELD_HAND && obj->kind == HN_FIELD_OBJ, "field kinds (hand, obj) expected");
@@ -1482,33 +1399,27 @@ static int render_dual_bwd_impl(const hn_field* hand, const hn_field* obj, const
     else if (side != nullptr)
         HN_TRY(gate_to(side, s));
     if (compact) {
-        set_launch_n_pts_dev(cr.n_dev);
-        set_launch_orig_idx(cr.idx);
-        set_launch_frame_seg(CompactRec::aligned_frames(n, n_frames, rpf * S) > 0 ? cr.seg : nullptr);
+        FieldLaunchOpts compacted = cr.opts(lo);
+        compacted.frame_seg = CompactRec::aligned_frames(n, n_frames, rpf * S) > 0 ? cr.seg : nullptr;
         // (the hand's colour network ignores the view direction, utils/fields.py:222-240: no d loss / d rays_d through it)
-        const int rc = bwd::field_eval_bwd(hand, cr.pts_c, rays_d, n + 1, 1, bt_inv, T_pose, n_frames, rpf * S, gs_c, gg_c, gr_c, gp_c, nullptr, g_bt_inv,
-                                           g_T_pose, bwh, bws_h, s, tp_h, cr.grad_c, cr.rgb_c);
-        set_launch_n_pts_dev(nullptr);
-        set_launch_orig_idx(nullptr);
-        set_launch_frame_seg(nullptr);
-        HN_TRY(rc);
+        HN_TRY(bwd::field_eval_bwd(hand, cr.pts_c, rays_d, n + 1, 1, bt_inv, T_pose, n_frames, rpf * S, gs_c, gg_c, gr_c, gp_c, nullptr, g_bt_inv, g_T_pose,
+                                   bwh, bws_h, s, compacted, tp_h, cr.grad_c, cr.rgb_c));
         if (want_rays) {
             hipLaunchKernelGGL(k_hand_scatter3, dim3((n + 255) / 256), dim3(256), 0, s, cr.pos, n, gp_c, gp_h);
             HN_LAUNCH_CHECK();
         }
     } else {
         HN_TRY(bwd::field_eval_bwd(hand, pts_h, rays_d, n, S, bt_inv, T_pose, n_frames, rpf * S, gs_h, gg_h, g_rgbh, gp_h, gdir_h, g_bt_inv,
-                                   g_T_pose, bwh, bws_h, s, tp_h, grad_h, rgb_h));
+                                   g_T_pose, bwh, bws_h, s, lo, tp_h, grad_h, rgb_h));
     }
     if (want_rays) HN_TRY(sample_points_bwd(z, gp_h, n_rays, S, 1, sample_dist, go_h, gdd_h, s));
     {
         // (the colour network's d loss / d rays_d per SAMPLE for f16x3 fields, summed per ray by k_obj_rays_bwd: no atomics)
         const bool per_sample = obj->v2_adj != nullptr;
-        set_launch_dir_per_sample(per_sample);
-        const int rc = bwd::field_eval_bwd(obj, pts_o, d_l, n, S, nullptr, nullptr, 1, n, gs_o, gg_o, g_rgbo, gp_o, per_sample ? gdir_os : gdir_o, nullptr,
-                                           nullptr, bwo, bws_o, so, tp_o, grad_o, rgb_o);
-        set_launch_dir_per_sample(false);
-        HN_TRY(rc);
+        FieldLaunchOpts obj_opts = lo;
+        obj_opts.dir_per_sample = per_sample;
+        HN_TRY(bwd::field_eval_bwd(obj, pts_o, d_l, n, S, nullptr, nullptr, 1, n, gs_o, gg_o, g_rgbo, gp_o, per_sample ? gdir_os : gdir_o, nullptr, nullptr, bwo,
+                                   bws_o, so, obj_opts, tp_o, grad_o, rgb_o));
         dir_per_sample = per_sample;
     }
     // behind the object's adjoint: the ray map and the adjoint of convert_obj_to_local in one launch
@@ -1542,7 +1453,7 @@ static int render_single_bwd_impl(const hn_field* f, const float* rays_o, const 
                                   const float* bt_inv, const float* T_pose, const float* z, const float* g_color,
                                   const float* g_wsum, const float* g_eik, float* g_params, float* g_inv_s, float* g_rays_o,
                                   float* g_rays_d, float* g_bt_inv, float* g_T_pose, void* workspace, size_t workspace_bytes,
-                                  hipStream_t s, size_t* need, const void* keep_block = nullptr, size_t keep_bytes = 0) {
+                                  hipStream_t s, size_t* need, const FieldLaunchOpts& lo, const void* keep_block = nullptr, size_t keep_bytes = 0) {
     HN_REQUIRE(n_rays >= 0 && S >= 1, "bad sizes");
     const size_t N = (size_t)n_rays * S, R3 = (size_t)n_rays * 3;
     Arena ar(workspace, workspace_bytes);
@@ -1668,11 +1579,11 @@ static int render_single_bwd_impl(const hn_field* f, const float* rays_o, const 
         // (the hand's colour network ignores the view direction: d loss / d rays_d through it is exactly 0)
         HN_CHECK_HIP(hipMemsetAsync(gdir, 0, R3 * sizeof(float), s));
         HN_TRY(bwd::field_eval_bwd(f, cr.pts_c, rays_d, n_c, 1, bt_inv, T_pose, 1, n_c, gs_c, gg_c, gr_c, gp_c, nullptr, gbt, gtp, bws, bws_bytes, s,
-                                   k_tape, k_grad, k_rgb, g_params, &mid, &mid2, k_sdf, k_feat));
+                                   lo, k_tape, k_grad, k_rgb, g_params, &mid, &mid2, k_sdf, k_feat));
         hipLaunchKernelGGL(k_hand_scatter3, dim3((n + 255) / 256), dim3(256), 0, s, cr.pos, n, gp_c, gp);
         HN_LAUNCH_CHECK();
     } else {
-        HN_TRY(bwd::field_eval_bwd(f, pts, rays_d, n, S, bt_inv, T_pose, 1, n, gs, gg, g_rgb, gp, gdir, gbt, gtp, bws, bws_bytes, s, k_tape,
+        HN_TRY(bwd::field_eval_bwd(f, pts, rays_d, n, S, bt_inv, T_pose, 1, n, gs, gg, g_rgb, gp, gdir, gbt, gtp, bws, bws_bytes, s, lo, k_tape,
                                    k_grad, k_rgb, g_params, &mid, &mid2, k_sdf, k_feat));
     }
     HN_TRY(sample_points_bwd(z, gp, n_rays, S, 1, sample_dist, go, gdd, s));
@@ -1834,7 +1745,7 @@ int hn_field_eval_bwd(const hn_field* f, const float* pts, const float* rays_d, 
                       float* g_T_pose, void* workspace, size_t workspace_bytes, hn_stream_t stream) {
     return hn::bwd::field_eval_bwd(f, pts, rays_d, n_pts, samples_per_ray, bt_inv, T_pose, n_frames, pts_per_frame, g_sdf, g_grad,
                                    g_rgb, g_pts, g_rays_d, g_bt_inv, g_T_pose, workspace, workspace_bytes,
-                                   reinterpret_cast<hipStream_t>(stream), nullptr, nullptr, nullptr);
+                                   reinterpret_cast<hipStream_t>(stream), resolve_launch_opts(), nullptr, nullptr, nullptr);
 }
 size_t hn_release_cached_memory(void) {
     hn::kept_counts_release();   // (the pinned words and events of hn_render_single_taped's counts: pool_trim synchronises the device first)
@@ -1865,13 +1776,13 @@ int hn_field_param_bwd(const hn_field* f, const float* pts, const float* rays_d,
     HN_REQUIRE(g_params != nullptr, "g_params is NULL");
     return hn::bwd::field_eval_bwd(f, pts, rays_d, n_pts, samples_per_ray, bt_inv, T_pose, n_frames, pts_per_frame, g_sdf, g_grad,
                                    g_rgb, g_pts, g_rays_d, g_bt_inv, g_T_pose, workspace, workspace_bytes,
-                                   reinterpret_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, g_params);
+                                   reinterpret_cast<hipStream_t>(stream), resolve_launch_opts(), nullptr, nullptr, nullptr, g_params);
 }
 size_t hn_render_single_bwd_workspace_bytes(const hn_field* f, int n_rays, int samples_per_ray) {
     if (f == nullptr || n_rays <= 0 || samples_per_ray <= 0) return 0;
     size_t need = 0;
     (void)render_single_bwd_impl(f, nullptr, nullptr, n_rays, samples_per_ray, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need);
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need, FieldLaunchOpts());
     return need;
 }
 int hn_render_single_bwd(const hn_field* f, const float* rays_o, const float* rays_d, int n_rays, int samples_per_ray,
@@ -1882,7 +1793,7 @@ int hn_render_single_bwd(const hn_field* f, const float* rays_o, const float* ra
     HN_REQUIRE(f != nullptr && f->raw != nullptr, "field has no folded weights");
     return render_single_bwd_impl(f, rays_o, rays_d, n_rays, samples_per_ray, sample_dist, bt_inv, T_pose, z_vals, g_color,
                                   g_weight_sum, g_gradient_error, g_params, g_inv_s, g_rays_o, g_rays_d, g_bt_inv, g_T_pose, workspace,
-                                  workspace_bytes, reinterpret_cast<hipStream_t>(stream), nullptr);
+                                  workspace_bytes, reinterpret_cast<hipStream_t>(stream), nullptr, resolve_launch_opts());
 }
 size_t hn_render_single_tape_bytes(const hn_field* f, int n_rays, int samples_per_ray) {
     if (f == nullptr || n_rays <= 0 || samples_per_ray <= 0 || !single_keep_applies(f)) return 0;
@@ -1897,7 +1808,7 @@ int hn_render_single_bwd_taped(const hn_field* f, const float* rays_o, const flo
     HN_REQUIRE(tape != nullptr, "hn_render_single_bwd_taped: tape is NULL");
     return render_single_bwd_impl(f, rays_o, rays_d, n_rays, samples_per_ray, sample_dist, bt_inv, T_pose, z_vals, g_color,
                                   g_weight_sum, g_gradient_error, g_params, g_inv_s, g_rays_o, g_rays_d, g_bt_inv, g_T_pose, workspace,
-                                  workspace_bytes, reinterpret_cast<hipStream_t>(stream), nullptr, tape, tape_bytes);
+                                  workspace_bytes, reinterpret_cast<hipStream_t>(stream), nullptr, resolve_launch_opts(), tape, tape_bytes);
 }
 float hn_field_inv_s(const hn_field* f) { return f ? f->inv_s : 0.f; }
 int hn_field_set_inv_s_device(hn_field* f, const float* inv_s_dev) {
@@ -1969,14 +1880,14 @@ int hn_field_sdf(const hn_field* f, const float* pts, int n_pts, const float* bt
                  int pts_per_frame, float* sdf, void* workspace, size_t workspace_bytes, hn_stream_t stream) {
     HN_REQUIRE(f != nullptr, "null field");
     return field_sdf(f, pts, n_pts, bt_inv, T_pose, n_frames, pts_per_frame, sdf, workspace, workspace_bytes,
-                     (hipStream_t)stream);
+                     (hipStream_t)stream, resolve_launch_opts());
 }
 int hn_field_eval(const hn_field* f, const float* pts, const float* rays_d, int n_pts, int samples_per_ray,
                   const float* bt_inv, const float* T_pose, int n_frames, int pts_per_frame, float* sdf, float* grad,
                   float* rgb, float* feat, void* workspace, size_t workspace_bytes, hn_stream_t stream) {
     HN_REQUIRE(f != nullptr, "null field");
     return field_eval(f, pts, rays_d, n_pts, samples_per_ray, bt_inv, T_pose, n_frames, pts_per_frame, sdf, grad, rgb,
-                      feat, workspace, workspace_bytes, (hipStream_t)stream);
+                      feat, workspace, workspace_bytes, (hipStream_t)stream, resolve_launch_opts());
 }
 
 int hn_alpha(const float* sdf, const float* grad, const float* rays_d, const float* dists, int n_pts,
@@ -2073,7 +1984,7 @@ int hn_field_eval_taped(const hn_field* f, const float* pts, const float* rays_d
     HN_REQUIRE(f != nullptr && tape != nullptr && tape_bytes >= field_tape(f, n_pts) && field_tape(f, n_pts) != 0,
                "hn_field_eval_taped: an HN_PREC_F16X3 field with its adjoint programs and a tape of hn_field_tape_bytes");
     return field_eval(f, pts, rays_d, n_pts, samples_per_ray, bt_inv, T_pose, n_frames, pts_per_frame, sdf, grad, rgb, nullptr, workspace,
-                      workspace_bytes, (hipStream_t)stream, tape, tape_bytes);
+                      workspace_bytes, (hipStream_t)stream, resolve_launch_opts(), tape, tape_bytes);
 }
 int hn_field_eval_bwd_taped(const hn_field* f, const float* pts, const float* rays_d, int n_pts, int samples_per_ray, const float* bt_inv,
                             const float* T_pose, int n_frames, int pts_per_frame, const float* g_sdf, const float* g_grad, const float* g_rgb,
@@ -2082,7 +1993,7 @@ int hn_field_eval_bwd_taped(const hn_field* f, const float* pts, const float* ra
     HN_REQUIRE(f != nullptr && tape != nullptr && g_grad != nullptr && g_rgb != nullptr && grad != nullptr && rgb != nullptr,
                "hn_field_eval_bwd_taped: tape, upstream gradients of all three outputs, and the evaluation's grad / rgb");
     return bwd::field_eval_bwd(f, pts, rays_d, n_pts, samples_per_ray, bt_inv, T_pose, n_frames, pts_per_frame, g_sdf, g_grad, g_rgb, g_pts, g_rays_d,
-                               g_bt_inv, g_T_pose, workspace, workspace_bytes, (hipStream_t)stream, tape, grad, rgb);
+                               g_bt_inv, g_T_pose, workspace, workspace_bytes, (hipStream_t)stream, resolve_launch_opts(), tape, grad, rgb);
 }
 size_t hn_fit_step_loss_scratch_bytes(int n_rays, int n_samples) { return hn::fit_step_loss_scratch_bytes(n_rays, n_samples); }
 int hn_fit_step_loss(const float* color, const float* weight_sum, const float* true_rgb, const float* true_mask, int n_rays, const float* sdf_hand,
@@ -2140,7 +2051,7 @@ size_t hn_render_single_workspace_bytes(const hn_field* f, int n_rays, int n_sam
     if (f == nullptr) return 0;
     if (render_single_impl(f, nullptr, nullptr, nullptr, n_rays, 0.0, 1.0, n_samples, n_importance,
                            n_importance > 0 ? 1 : 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, 0, nullptr, &need) != HN_OK)
+                           nullptr, nullptr, 0, nullptr, &need, FieldLaunchOpts(), 0) != HN_OK)
         return 0;
     return need;
 }
@@ -2149,9 +2060,11 @@ int hn_render_single(const hn_field* f, const float* rays_o, const float* rays_d
                      const float* T_pose, float* color, float* cdf, float* weight_sum, float* weight_max,
                      float* gradient_error, float* z_vals, void* workspace, size_t workspace_bytes, hn_stream_t stream) {
     HN_REQUIRE(f != nullptr, "null field");
+    int live_first = 1;
+    const FieldLaunchOpts lo = resolve_launch_opts(&live_first);
     return render_single_impl(f, rays_o, rays_d, t_rand, n_rays, near, far, n_samples, n_importance, up_sample_steps,
                               bt_inv, T_pose, color, cdf, weight_sum, weight_max, gradient_error, z_vals, workspace,
-                              workspace_bytes, (hipStream_t)stream, nullptr);
+                              workspace_bytes, (hipStream_t)stream, nullptr, lo, live_first);
 }
 
 int hn_render_single_taped(const hn_field* f, const float* rays_o, const float* rays_d, const float* t_rand, int n_rays,
@@ -2161,10 +2074,11 @@ int hn_render_single_taped(const hn_field* f, const float* rays_o, const float* 
                            hn_stream_t stream) {
     HN_REQUIRE(f != nullptr, "null field");
     HN_REQUIRE(tape != nullptr, "hn_render_single_taped: tape is NULL");
-    ThreePassScope three_pass(true);
+    FieldLaunchOpts lo = resolve_launch_opts();
+    lo.three_pass = true;   // (a render that keeps a tape: HN_PREC_F16 fields take the fp32-equivalent kernels)
     return render_single_impl(f, rays_o, rays_d, t_rand, n_rays, near, far, n_samples, n_importance, up_sample_steps,
                               bt_inv, T_pose, color, cdf, weight_sum, weight_max, gradient_error, z_vals, workspace,
-                              workspace_bytes, (hipStream_t)stream, nullptr, tape, tape_bytes);
+                              workspace_bytes, (hipStream_t)stream, nullptr, lo, 0, tape, tape_bytes);   // (live_first: never with a tape)
 }
 
 size_t hn_render_dual_workspace_bytes(const hn_field* hand, const hn_field* obj, int n_rays, int n_samples,
@@ -2173,7 +2087,7 @@ size_t hn_render_dual_workspace_bytes(const hn_field* hand, const hn_field* obj,
     if (hand == nullptr || obj == nullptr) return 0;
     if (render_dual_impl(hand, obj, nullptr, nullptr, nullptr, 1, n_rays, 0.0, 1.0, n_samples, n_importance,
                          n_importance > 0 ? 1 : 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need) != HN_OK)
+                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need, FieldLaunchOpts()) != HN_OK)
         return 0;
     return need;
 }
@@ -2183,7 +2097,7 @@ size_t hn_render_dual_bwd_workspace_bytes(const hn_field* hand, const hn_field* 
     if (render_dual_bwd_impl(hand, obj, nullptr, nullptr, 1, n_rays, samples_per_ray, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr,
                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
-                             &need) != HN_OK)
+                             &need, FieldLaunchOpts()) != HN_OK)
         return 0;
     return need;
 }
@@ -2199,7 +2113,8 @@ int hn_render_dual_bwd(const hn_field* hand, const hn_field* obj, const float* r
     return render_dual_bwd_impl(hand, obj, rays_o, rays_d, n_frames, rays_per_frame, samples_per_ray, sample_dist, bt_inv, T_pose, Ro,
                                 To, z_vals, sdf_hand, grad_hand, rgb_hand, alpha_hand, sdf_obj, grad_obj, rgb_obj, alpha_obj,
                                 g_color, g_weight_sum, g_sdf_hand, g_sdf_obj, g_grad_hand, g_grad_obj, g_gradient_error, g_rays_o,
-                                g_rays_d, g_bt_inv, g_T_pose, g_Ro, g_To, workspace, workspace_bytes, (hipStream_t)stream, nullptr, tape, flags);
+                                g_rays_d, g_bt_inv, g_T_pose, g_Ro, g_To, workspace, workspace_bytes, (hipStream_t)stream, nullptr, resolve_launch_opts(),
+                                tape, flags);
 }
 int hn_render_dual_aux_offsets(const hn_field* hand, const hn_field* obj, int n_rays, int n_samples, int n_importance,
                                int up_sample_steps, size_t* offsets4) {
@@ -2207,7 +2122,7 @@ int hn_render_dual_aux_offsets(const hn_field* hand, const hn_field* obj, int n_
     size_t need = 0;
     return render_dual_impl(hand, obj, nullptr, nullptr, nullptr, 1, n_rays, 0.0, 1.0, n_samples, n_importance,
                             n_importance > 0 ? up_sample_steps : 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need, offsets4);
+                            nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need, FieldLaunchOpts(), offsets4);
 }
 int hn_render_dual_compact_offsets(const hn_field* hand, const hn_field* obj, int n_rays, int n_samples, int n_importance,
                                    int up_sample_steps, size_t* offsets2) {
@@ -2215,7 +2130,7 @@ int hn_render_dual_compact_offsets(const hn_field* hand, const hn_field* obj, in
     size_t need = 0;
     return render_dual_impl(hand, obj, nullptr, nullptr, nullptr, 1, n_rays, 0.0, 1.0, n_samples, n_importance,
                             n_importance > 0 ? up_sample_steps : 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need, nullptr, nullptr, 0, offsets2);
+                            nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &need, FieldLaunchOpts(), nullptr, nullptr, 0, offsets2);
 }
 int hn_render_dual(const hn_field* hand, const hn_field* obj, const float* rays_o, const float* rays_d,
                    const float* t_rand, int n_frames, int rays_per_frame, double near, double far, int n_samples,
@@ -2224,11 +2139,12 @@ int hn_render_dual(const hn_field* hand, const hn_field* obj, const float* rays_
                    float* grad_hand, float* grad_obj, float* gradient_error, float* z_vals, void* workspace,
                    size_t workspace_bytes, void* tape, size_t tape_bytes, int flags, hn_stream_t stream) {
     HN_REQUIRE(hand != nullptr && obj != nullptr, "null field");
-    ThreePassScope three_pass(tape != nullptr);
+    FieldLaunchOpts lo = resolve_launch_opts();
+    lo.three_pass = tape != nullptr;   // (a render that keeps a tape: HN_PREC_F16 fields take the fp32-equivalent kernels)
     return render_dual_impl(hand, obj, rays_o, rays_d, t_rand, n_frames, rays_per_frame, near, far, n_samples,
                             n_importance, up_sample_steps, bt_inv, T_pose, Ro, To, batch_quirk, color, weight_sum,
                             sdf_hand, sdf_obj, grad_hand, grad_obj, gradient_error, z_vals, workspace, workspace_bytes,
-                            (hipStream_t)stream, nullptr, nullptr, tape, tape_bytes, nullptr, flags);
+                            (hipStream_t)stream, nullptr, lo, nullptr, tape, tape_bytes, nullptr, flags);
 }
 size_t hn_render_dual_tape_bytes(const hn_field* hand, const hn_field* obj, int n_rays, int samples_per_ray) {
     if (hand == nullptr || obj == nullptr || n_rays <= 0 || samples_per_ray <= 0) return 0;

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/honerf.h"
+#include "hn_launch_opts.h"   // FieldLaunchOpts: the options of a field launch, passed down as an argument
 
 namespace hn {
 
@@ -37,27 +38,7 @@ void set_error(const char* fmt, ...);
 // Per-device state (one process may drive several GPUs, from several threads).
 int current_device();          // hipGetDevice, -1 on failure
 int device_cus();              // CU count of the CURRENT device (cached per device; 0 if none)
-// Device-side sample count of the NEXT hand-field launches of this host thread (hn_api.hip sets it around the launches over a
-// compacted sample list and clears it again); NULL otherwise.
-const int* launch_n_pts_dev();
-void set_launch_n_pts_dev(const int* p);
-const int* launch_orig_idx();
-void set_launch_orig_idx(const int* p);
-// The frame table of a FRAME-ALIGNED compact list (hn_api.hip, k_hand_compact_write: [first slot per frame, af + 1 | live samples per
-// frame, af]; n_pts_dev[2] = af) for the next hand-field ADJOINT launch of this host thread: k_pose_part_reduce takes a frame's rows
-// from it.  NULL: a dense list, or the plain compact layout of a one-frame launch.
-const int* launch_frame_seg();
-void set_launch_frame_seg(const int* p);
-bool launch_dir_per_sample();     // hn_api.hip: the object adjoint launch writes d loss / d rays_d per sample (set around the launch)
-bool launch_three_pass();         // hn_api.hip: inside a render that keeps a TAPE (a backward pass follows) every launch of an HN_PREC_F16 field,
-                                  // the sdf-only ones of the importance rounds included, takes the fp32-equivalent kernels: the differentiable
-                                  // render of such a field is the HN_PREC_F16X3 field's, bit for bit
 int quad_max_blocks_override();   // hn_debug_quad_max_blocks: -1 = default selection of the latency-form kernels
-int uniform_stash_mode();         // hn_api.hip: HONERF_UNIFORM_STASH, read per launch (Hand2Args::ustash): 0 = every wave of the hand evaluation
-                                  // kernel moves its stash at full width; 2 = a wave whose samples are all far keeps one column, in
-                                  // place; unset or 1 = that column packed into whole cache lines
-int far_tiles_mode();             // hn_api.hip: HONERF_FAR_TILES, read per launch (Hand2Args::far_tiles): 0 = every tile of the hand evaluation
-                                  // kernel runs the general tile program; unset or 1 = all-far tiles run their own
 int pace_phantom_members();    // hn_debug_pace_phantom: members that never arrive at the XCD meetings (timeout-path test hook), 0 = off
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device): `mask` is the kernel's own
 // bit set of devices already configured (a static std::atomic<uint64_t> next to the launch).

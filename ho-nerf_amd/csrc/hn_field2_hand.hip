@@ -13,6 +13,7 @@
 #include <atomic>
 
 #include "hn_common.h"
+#include "hn_field_launch.h"
 #if !defined(HN_HAND_ADJ_TU) && !defined(HN_HAND_F16_TU) && !defined(HN_HAND_QUAD_TU) && !defined(HN_MFMA16)
 #define HN_MFMA16 HN_HAND_EVAL_MFMA16   // the evaluation kernels (MODE 0, 1); the adjoint translation unit keeps 32x32x16
 #endif
@@ -72,10 +73,10 @@ struct Hand2Args {
     float4* scratch;
     int dbg;
     int cull;   // hn_field_set_culling
-    int ustash; // HONERF_UNIFORM_STASH (hn_api.hip: uniform_stash_mode), the full evaluation (MODE 1) only: a wave whose samples are all far
+    int ustash; // HONERF_UNIFORM_STASH (FieldLaunchOpts::uniform_stash), the full evaluation (MODE 1) only: a wave whose samples are all far
                 // moves one column of its stash per half instead of 32.  Holds StashT::umask of such a wave, USTASH_COLS, plus -- packed
                 // form -- StashT::ush in its low four bits (USTASH_SHIFT); 0 = off
-    int far_tiles;   // HONERF_FAR_TILES (hn_api.hip: far_tiles_mode) and the packed uniform stash, the full evaluation (MODE 1) only: a tile
+    int far_tiles;   // HONERF_FAR_TILES (FieldLaunchOpts::far_tiles) and the packed uniform stash, the full evaluation (MODE 1) only: a tile
                      // whose four waves are all far runs the all-far tile program (FarStash below); 0 = every tile runs the general one
     // adjoint (MODE 2): upstream gradients in, input / pose gradients out
     const float* g_sdf;    // [n]
@@ -91,7 +92,7 @@ struct Hand2Args {
                            // the wave's first frame [0] and of the frame behind it [1] (a wave of a dense multi-frame list may cross one
                            // frame boundary); k_pose_part_reduce adds a frame's rows in a fixed order that depends on that frame's own
                            // tiles only: the same bits in every run AND whatever other frames share the launch.  Atomics otherwise.
-    const int* frame_seg;  // NULL, or the frame table of a frame-aligned compact list (hn_common.h: launch_frame_seg)
+    const int* frame_seg;  // NULL, or the frame table of a frame-aligned compact list (FieldLaunchOpts::frame_seg)
     // MODE 5 (the adjoint from a tape that also leaves the PER-LAYER SIGNALS of the parameter gradients): HSG_COUNT row-major
     // [n, 256] fp32 arrays `sig + k * sig_pitch` (enum below; the layout of hn_field2_obj.hip's), unscaled, and gb [n,3] (the adjoint of
     // d sdf / d pts incl. the colour network's share: J gb is the forward-direction sweep's input)
@@ -1491,7 +1492,7 @@ static int taped_grid(int n_pts, int n_cus) {
 }
 
 static void hand2_common_args(Hand2Args& a, const hn_field* f, const float* pts, int n_pts, const float* bt_inv, const float* T_pose,
-                              int n_frames, int pts_per_frame, void* workspace) {
+                              int n_frames, int pts_per_frame, void* workspace, const FieldLaunchOpts& lo) {
     a.pts = pts;
     a.bt_inv = bt_inv;
     a.T_pose = T_pose;
@@ -1504,8 +1505,8 @@ static void hand2_common_args(Hand2Args& a, const hn_field* f, const float* pts,
     a.dbg = 0;
     a.cull = f->cull_far_field;
     a.xsync = nullptr;
-    a.n_pts_dev = launch_n_pts_dev();   // (set by the caller around a launch over a compacted sample list, else NULL)
-    a.orig_idx = launch_orig_idx();
+    a.n_pts_dev = lo.n_pts_dev;   // (a launch over a compacted sample list, else NULL)
+    a.orig_idx = lo.orig_idx;
 }
 
 #if defined(HN_HAND_QUAD_TU)    // hn_field2_hand_q.hip: only the device helpers above are wanted
@@ -1536,20 +1537,21 @@ size_t field2_hand_workspace_bytes(int n_pts, int n_cus) {
 }
 
 int launch_field2_hand_taped(const hn_field* f, const float* pts, int n_pts, const float* bt_inv, const float* T_pose, int n_frames,
-                             int pts_per_frame, float* sdf, float* grad, float* rgb, float* feat, void* tape, size_t tape_bytes, hipStream_t stream);
+                             int pts_per_frame, float* sdf, float* grad, float* rgb, float* feat, void* tape, size_t tape_bytes, hipStream_t stream,
+                             const FieldLaunchOpts& lo);
 
 // tape != NULL (full evaluation only): the evaluation keeps its tape there (field2_hand_tape_bytes) for a later
 // adjoint launch, instead of using the workspace (k_field2_hand<3>, compiled in hn_field2_hand_adj.hip)
 int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const float* bt_inv, const float* T_pose,
                        int n_frames, int pts_per_frame, float* sdf, float* grad, float* rgb, float* feat, void* workspace,
-                       size_t workspace_bytes, bool full, hipStream_t stream, void* tape = nullptr, size_t tape_bytes = 0) {
+                       size_t workspace_bytes, bool full, hipStream_t stream, const FieldLaunchOpts& lo, void* tape, size_t tape_bytes) {
     if (full && tape != nullptr && n_pts > 0)
-        return launch_field2_hand_taped(f, pts, n_pts, bt_inv, T_pose, n_frames, pts_per_frame, sdf, grad, rgb, feat, tape, tape_bytes, stream);
+        return launch_field2_hand_taped(f, pts, n_pts, bt_inv, T_pose, n_frames, pts_per_frame, sdf, grad, rgb, feat, tape, tape_bytes, stream, lo);
     if (n_pts <= 0) return HN_OK;
     HN_REQUIRE(bt_inv != nullptr && T_pose != nullptr && n_frames >= 1 && pts_per_frame >= 1,
                "hand field needs bt_inv / T_pose and frame sizes");
     Hand2Args a{};
-    hand2_common_args(a, f, pts, n_pts, bt_inv, T_pose, n_frames, pts_per_frame, workspace);
+    hand2_common_args(a, f, pts, n_pts, bt_inv, T_pose, n_frames, pts_per_frame, workspace, lo);
     a.blob = reinterpret_cast<const char*>(full ? f->v2_full : f->v2_sdf);
     a.blob_bytes = full ? f->v2_full_bytes : f->v2_sdf_bytes;
     if (a.blob == nullptr) {
@@ -1560,9 +1562,9 @@ int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const flo
     a.grad = grad;
     a.rgb = rgb;
     a.feat = feat;
-    const int us_mode = full ? uniform_stash_mode() : 0;   // (the full evaluation kernels alone are built with it)
+    const int us_mode = full ? lo.uniform_stash : 0;   // (the full evaluation kernels alone are built with it)
     a.ustash = us_mode == 0 ? 0 : (us_mode == 2 ? USTASH_COLS : (USTASH_COLS | USTASH_SHIFT));
-    a.far_tiles = (us_mode == 1 && far_tiles_mode() != 0) ? 1 : 0;   // (the all-far tile program goes with the default, packed form)
+    a.far_tiles = (us_mode == 1 && lo.far_tiles != 0) ? 1 : 0;   // (the all-far tile program goes with the default, packed form)
 #ifdef HN_DEBUG_HOOKS
     {
         const char* e = getenv("HN_DBG");
@@ -1579,7 +1581,7 @@ int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const flo
     }
     // a launch too small to fill the chip: the latency form (bit-identical results; its stash fits the same workspace)
     const int n_blocks = (n_pts + 31) / 32;
-    const bool single_pass = f->single_pass && !launch_three_pass();   // HN_PREC_F16, outside a taped render
+    const bool single_pass = f->single_pass && !lo.three_pass;   // HN_PREC_F16, outside a taped render
     if (!full && !single_pass && n_blocks <= quad_max_blocks(n_cus) && field2_hand_q_workspace_bytes(n_blocks, n_cus) <= workspace_bytes)
         return launch_field2_hand_q(a, n_blocks, n_cus, stream);
     // XCD pacing: launches of many tiles per workgroup (the image-sized ones), where the workspace has the room
@@ -1630,7 +1632,8 @@ size_t field2_hand_tape_bytes(int n_pts) {
 
 // the full evaluation that keeps its tape (MODE 3)
 int launch_field2_hand_taped(const hn_field* f, const float* pts, int n_pts, const float* bt_inv, const float* T_pose, int n_frames,
-                             int pts_per_frame, float* sdf, float* grad, float* rgb, float* feat, void* tape, size_t tape_bytes, hipStream_t stream) {
+                             int pts_per_frame, float* sdf, float* grad, float* rgb, float* feat, void* tape, size_t tape_bytes, hipStream_t stream,
+                             const FieldLaunchOpts& lo) {
     HN_REQUIRE(bt_inv != nullptr && T_pose != nullptr && n_frames >= 1 && pts_per_frame >= 1,
                "hand field needs bt_inv / T_pose and frame sizes");
     HN_REQUIRE(f->v2_full != nullptr, "field was not created with HN_PREC_F16X3");
@@ -1639,7 +1642,7 @@ int launch_field2_hand_taped(const hn_field* f, const float* pts, int n_pts, con
         return HN_ENOMEM;
     }
     Hand2Args a{};
-    hand2_common_args(a, f, pts, n_pts, bt_inv, T_pose, n_frames, pts_per_frame, tape);
+    hand2_common_args(a, f, pts, n_pts, bt_inv, T_pose, n_frames, pts_per_frame, tape, lo);
     a.blob = reinterpret_cast<const char*>(f->v2_tape != nullptr ? f->v2_tape : f->v2_full);
     a.blob_bytes = f->v2_tape != nullptr ? f->v2_tape_bytes : f->v2_full_bytes;
     a.sdf = sdf;
@@ -1661,8 +1664,8 @@ int launch_field2_hand_taped(const hn_field* f, const float* pts, int n_pts, con
 int launch_field2_hand_adj(const hn_field* f, const float* pts, int n_pts, const float* bt_inv, const float* T_pose, int n_frames,
                            int pts_per_frame, const float* g_sdf, const float* g_grad, const float* g_rgb, float* g_pts,
                            float* g_bt_inv, float* g_T_pose, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                           const void* tape = nullptr, const float* grad = nullptr, const float* rgb = nullptr, float* sig = nullptr,
-                           size_t sig_pitch = 0, float* gb_out = nullptr) {
+                           const FieldLaunchOpts& lo, const void* tape, const float* grad, const float* rgb, float* sig, size_t sig_pitch,
+                           float* gb_out) {
     if (n_pts <= 0) return HN_OK;
     HN_REQUIRE((tape != nullptr ? f->v2_adjonly : f->v2_adj) != nullptr, "field has no adjoint program");
     HN_REQUIRE(tape == nullptr || (grad != nullptr && rgb != nullptr), "the adjoint from a tape needs the evaluation's grad / rgb");
@@ -1671,7 +1674,7 @@ int launch_field2_hand_adj(const hn_field* f, const float* pts, int n_pts, const
     a.sig = sig;
     a.sig_pitch = sig_pitch;
     a.gb_out = gb_out;
-    hand2_common_args(a, f, pts, n_pts, bt_inv, T_pose, n_frames, pts_per_frame, workspace);
+    hand2_common_args(a, f, pts, n_pts, bt_inv, T_pose, n_frames, pts_per_frame, workspace, lo);
     a.blob = reinterpret_cast<const char*>(f->v2_adj);
     a.blob_bytes = f->v2_adj_bytes;
     a.g_sdf = g_sdf;
@@ -1691,7 +1694,7 @@ int launch_field2_hand_adj(const hn_field* f, const float* pts, int n_pts, const
     // at most two), a compact multi-frame list only in its frame-aligned layout (hn_api.hip), up to POSE_MAX_TILES tiles; otherwise
     // float atomics.  The rows live behind the stash in the workspace (the adjoint from a tape has the whole workspace free).
     const size_t stash_bytes = (size_t)grid * WG_WAVES * HAND2_SLOTS_ADJ * SLOT_F4 * sizeof(float4);
-    a.frame_seg = launch_frame_seg();
+    a.frame_seg = lo.frame_seg;
     const size_t rows_bytes = pose_part_bytes(n_pts);
     const bool frames_ok = n_frames == 1 || (a.n_pts_dev == nullptr ? pts_per_frame >= 32 : a.frame_seg != nullptr);
     const bool det = n_frames >= 1 && frames_ok && rows_bytes != 0 && (g_bt_inv != nullptr || g_T_pose != nullptr) && workspace != nullptr &&

@@ -9,6 +9,7 @@
 
 #include <atomic>
 
+#include "hn_field_launch.h"
 #include "hn_mlp2.h"
 #ifndef HN_PARK_AGPR
 #define HN_PARK_AGPR 1
@@ -1144,7 +1145,7 @@ size_t field2_obj_tape_bytes(int n_pts) {
 // using the workspace
 int launch_field2_obj(const hn_field* f, const float* pts, const float* rays_d, int n_pts, int spr, float* sdf,
                       float* grad, float* rgb, float* feat, void* workspace, size_t workspace_bytes, bool full,
-                      hipStream_t stream, void* tape = nullptr, size_t tape_bytes = 0) {
+                      hipStream_t stream, const FieldLaunchOpts& lo, void* tape, size_t tape_bytes) {
     if (n_pts <= 0) return HN_OK;
     Obj2Args a{};
     a.pts = pts;
@@ -1201,7 +1202,7 @@ int launch_field2_obj(const hn_field* f, const float* pts, const float* rays_d, 
     }
     // an sdf-only launch too small to fill the chip: the latency form (hn_field2_obj_q.hip; bit-identical results).  Not for a
     // single-pass field: sdf() and the sdf of a full evaluation take the same passes
-    const bool single_pass = f->single_pass && !launch_three_pass();   // HN_PREC_F16, outside a taped render
+    const bool single_pass = f->single_pass && !lo.three_pass;   // HN_PREC_F16, outside a taped render
     if (!single_pass) {
         const int n_blocks = (n_pts + 31) / 32;
         const int qmax = quad_max_blocks_override();
@@ -1229,8 +1230,8 @@ size_t field2_obj_adj_workspace_bytes(int n_pts, int n_cus) {
 // `grad`, `rgb` are passed back in.
 int launch_field2_obj_adj(const hn_field* f, const float* pts, const float* rays_d, int n_pts, int spr, const float* g_sdf,
                           const float* g_grad, const float* g_rgb, float* g_pts, float* g_rays_d, void* workspace,
-                          size_t workspace_bytes, hipStream_t stream, const void* tape = nullptr, const float* grad = nullptr,
-                          const float* rgb = nullptr, float* sig = nullptr, size_t sig_pitch = 0, float* gb_out = nullptr) {
+                          size_t workspace_bytes, hipStream_t stream, const FieldLaunchOpts& lo, const void* tape, const float* grad,
+                          const float* rgb, float* sig, size_t sig_pitch, float* gb_out) {
     if (n_pts <= 0) return HN_OK;
     HN_REQUIRE((tape != nullptr ? f->v2_adjonly : f->v2_adj) != nullptr, "field has no adjoint program");
     HN_REQUIRE(tape == nullptr || (grad != nullptr && rgb != nullptr), "the adjoint from a tape needs the evaluation's grad / rgb");
@@ -1258,7 +1259,7 @@ int launch_field2_obj_adj(const hn_field* f, const float* pts, const float* rays
     int n_cus = device_cus();
     if (n_cus <= 0) n_cus = 256;
     const int grid = obj2_grid(n_pts, n_cus);
-    a.dir_per_sample = launch_dir_per_sample() ? 1 : 0;
+    a.dir_per_sample = lo.dir_per_sample ? 1 : 0;
     if (g_rays_d != nullptr && !a.dir_per_sample) HN_CHECK_HIP(hipMemsetAsync(g_rays_d, 0, (size_t)(n_pts / a.spr) * 3 * sizeof(float), stream));
     if (tape != nullptr) {
         a.blob = reinterpret_cast<const char*>(f->v2_adjonly);

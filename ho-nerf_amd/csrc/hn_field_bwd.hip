@@ -17,29 +17,9 @@
 #include <type_traits>
 
 #include "hn_common.h"
+#include "hn_field_launch.h"
 
 namespace hn {
-namespace v2 {
-size_t field2_obj_adj_workspace_bytes(int n_pts, int n_cus);
-int launch_field2_obj_adj(const hn_field* f, const float* pts, const float* rays_d, int n_pts, int spr, const float* g_sdf,
-                          const float* g_grad, const float* g_rgb, float* g_pts, float* g_rays_d, void* workspace,
-                          size_t workspace_bytes, hipStream_t stream, const void* tape, const float* grad, const float* rgb,
-                          float* sig = nullptr, size_t sig_pitch = 0, float* gb_out = nullptr);
-int launch_field2_obj(const hn_field*, const float*, const float*, int, int, float*, float*, float*, float*, void*, size_t, bool, hipStream_t, void*, size_t);
-size_t field2_obj_tape_bytes(int n_pts);
-int field2_obj_signal_arrays();
-size_t field2_hand_adj_workspace_bytes(int n_pts, int n_cus);
-int launch_field2_hand_adj(const hn_field* f, const float* pts, int n_pts, const float* bt_inv, const float* T_pose, int n_frames,
-                           int pts_per_frame, const float* g_sdf, const float* g_grad, const float* g_rgb, float* g_pts,
-                           float* g_bt_inv, float* g_T_pose, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                           const void* tape, const float* grad, const float* rgb, float* sig = nullptr, size_t sig_pitch = 0,
-                           float* gb_out = nullptr);
-int launch_field2_hand(const hn_field*, const float*, int, const float*, const float*, int, int, float*, float*, float*, float*, void*, size_t, bool,
-                       hipStream_t, void* tape, size_t tape_bytes);
-size_t field2_hand_tape_bytes(int n_pts);
-int field2_hand_signal_arrays();
-size_t field2_hand_pose_rows_bytes(int n_pts);
-}
 namespace bwd {
 
 // The fused adjoint kernels (hn_field2_*.hip, MODE 2) serve HN_PREC_F16X3 fields; the launch sequence below stays as
@@ -1154,21 +1134,10 @@ size_t field_bwd_workspace_bytes(const hn_field* f, int n) {
     return need;
 }
 
-// mid (with g_params only): called once the forward tape stands (z8 [n,257]: column 0 = sdf * scale, then the feature
-// vector; d sdf / d pts [n,3]; the colour network's pre-sigmoid output [n,3]) and before any upstream gradient is read:
-// the caller derives g_sdf / g_grad / g_rgb from these values there (hn_render_single_bwd: alpha stage and compositing
-// and their adjoints), so a training step's backward pass does not evaluate the field a second time.
-typedef std::function<int(const float* z8, const float* grad, const float* rgb_pre)> MidHook;
-// ... and for the fused form of the parameter-gradient path (below): the taped evaluation's outputs themselves (sdf [n], d sdf / d pts [n,3],
-// rgb [n,3])
-typedef std::function<int(const float* sdf, const float* grad, const float* rgb)> MidHook2;
-
-// tape / grad / rgb (HN_PREC_F16X3 only, may be NULL): the tape a taped evaluation of the same points left and that
-// evaluation's outputs -- the adjoint then runs alone instead of re-evaluating the field first
 int field_eval_bwd(const hn_field* f, const float* pts, const float* rays_d, int n, int spr, const float* bt_inv,
                    const float* T_pose, int n_frames, int pts_per_frame, const float* g_sdf, const float* g_grad,
                    const float* g_rgb, float* g_pts, float* g_rays_d, float* g_bt_inv, float* g_T_pose, void* workspace,
-                   size_t workspace_bytes, hipStream_t s, const void* tape, const float* grad, const float* rgb, float* g_params,
+                   size_t workspace_bytes, hipStream_t s, const FieldLaunchOpts& lo, const void* tape, const float* grad, const float* rgb, float* g_params,
                    const MidHook* mid, const MidHook2* mid2, const float* sdf_t, const float* feat_t) {
     HN_REQUIRE(f != nullptr && f->raw != nullptr, "field has no folded weights");
     const bool obj = f->kind == HN_FIELD_OBJ;
@@ -1219,9 +1188,9 @@ int field_eval_bwd(const hn_field* f, const float* pts, const float* rays_d, int
             b.rgb = const_cast<float*>(rgb);
             b.feat = const_cast<float*>(feat_t);
         } else if (obj) {
-            HN_TRY_RC(v2::launch_field2_obj(f, pts, rays_d, n, spr, b.sdf, b.grad, b.rgb, b.feat, nullptr, 0, true, s, b.tape, b.tape_bytes));
+            HN_TRY_RC(v2::launch_field2_obj(f, pts, rays_d, n, spr, b.sdf, b.grad, b.rgb, b.feat, nullptr, 0, true, s, lo, b.tape, b.tape_bytes));
         } else {
-            HN_TRY_RC(v2::launch_field2_hand(f, pts, n, bt_inv, T_pose, n_frames, pts_per_frame, b.sdf, b.grad, b.rgb, b.feat, nullptr, 0, true, s, b.tape,
+            HN_TRY_RC(v2::launch_field2_hand(f, pts, n, bt_inv, T_pose, n_frames, pts_per_frame, b.sdf, b.grad, b.rgb, b.feat, nullptr, 0, true, s, lo, b.tape,
                                              b.tape_bytes));
         }
         if (mid2 != nullptr) {
@@ -1232,14 +1201,14 @@ int field_eval_bwd(const hn_field* f, const float* pts, const float* rays_d, int
         // 3. the adjoint from the tape, leaving the signals (its sig arrays are written for every valid sample; columns 193 .. 255 of the
         //    object field's 193-wide layer-3 arrays are never read)
         if (obj) {
-            HN_TRY_RC(v2::launch_field2_obj_adj(f, pts, rays_d, n, spr, g_sdf, g_grad, g_rgb, g_pts, g_rays_d, nullptr, 0, s, b.tape, b.grad, b.rgb, b.sig,
+            HN_TRY_RC(v2::launch_field2_obj_adj(f, pts, rays_d, n, spr, g_sdf, g_grad, g_rgb, g_pts, g_rays_d, nullptr, 0, s, lo, b.tape, b.grad, b.rgb, b.sig,
                                                 b.pitch, b.gb));
         } else {
             // (the hand's colour network ignores the view direction, utils/fields.py:222-240: its gradient is exactly 0; the pose gradients
             //  accumulate into the caller's zeroed g_bt_inv / g_T_pose)
             if (g_rays_d != nullptr) HN_CHECK_HIP(hipMemsetAsync(g_rays_d, 0, (size_t)(n / spr) * 3 * sizeof(float), s));
             HN_TRY_RC(v2::launch_field2_hand_adj(f, pts, n, bt_inv, T_pose, n_frames, pts_per_frame, g_sdf, g_grad, g_rgb, g_pts, g_bt_inv, g_T_pose, b.rows,
-                                                 b.rows_bytes, s, b.tape, b.grad, b.rgb, b.sig, b.pitch, b.gb));
+                                                 b.rows_bytes, s, lo, b.tape, b.grad, b.rgb, b.sig, b.pitch, b.gb));
         }
         // 4. what the outer products pair the signals with: the input features, the colour seed, J gb, g_sdf / scale
         if (obj) {
@@ -1316,11 +1285,11 @@ int field_eval_bwd(const hn_field* f, const float* pts, const float* rays_d, int
     if (g_params == nullptr && fused_adjoint(f, sdf_only)) {
         if (obj)
             return v2::launch_field2_obj_adj(f, pts, rays_d, n, spr, g_sdf, g_grad, g_rgb, g_pts, g_rays_d, workspace, workspace_bytes, s,
-                                             tape, grad, rgb);
+                                             lo, tape, grad, rgb);
         // the hand's colour network ignores the view direction (utils/fields.py:222-240): its gradient is exactly 0
         if (g_rays_d != nullptr) HN_CHECK_HIP(hipMemsetAsync(g_rays_d, 0, (size_t)(n / spr) * 3 * sizeof(float), s));
         return v2::launch_field2_hand_adj(f, pts, n, bt_inv, T_pose, n_frames, pts_per_frame, g_sdf, g_grad, g_rgb, g_pts, g_bt_inv,
-                                          g_T_pose, workspace, workspace_bytes, s, tape, grad, rgb);
+                                          g_T_pose, workspace, workspace_bytes, s, lo, tape, grad, rgb);
     }
     Arena ar{reinterpret_cast<char*>(workspace), 0, workspace_bytes};
     Bufs b;

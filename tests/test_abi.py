@@ -59,15 +59,31 @@ def test_product_never_imports_oracle():
                 assert not re.search(r'^\s*(from|import)\s+oracle\b', text, flags=re.M), f
 
 
+def test_field_launch_options_are_arguments_not_ambient_state():
+    """what a field launch needs beside its arrays reaches the launcher as a FieldLaunchOpts argument.  Nothing under
+    csrc/ sets or reads per-thread launch state, and the HONERF_* environment switches are read in one place, the resolver."""
+    csrc = os.path.join(ROOT, 'ho-nerf_amd', 'csrc')
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f))}
+    assert len(text) > 30
+    assert [f for f, t in text.items() if 'getenv("HONERF_' in t] == ['hn_launch_opts.h']
+    for f, t in text.items():
+        assert not re.search(r'set_launch_\w+', t), f
+        assert not re.search(r'launch_(n_pts_dev|orig_idx|frame_seg|dir_per_sample|three_pass)\s*\(', t), f
+    # the two per-thread variables that remain: the last error message and the packer's scratch switch
+    tl = sorted((f, line.strip().split('=')[0].split()[-1]) for f, t in text.items() for line in t.splitlines() if 'thread_local' in line)
+    assert tl == [('hn_api.hip', 'g_err[512]'), ('hn_pack2.hip', 'g_s16')], tl
+
+
 def test_host_side_code_is_clean_under_address_and_ub_sanitizers():
     """SURVEY 5 (sanitizers on the CPU side only: GPU ASan is not available on the pool): the pure-host pieces of the library
     -- the layout planner of the f16x3 weight-stream packer (hn_pack2.hip compiled host-only) and the pose-chain header through
-    the oracle's double-precision entry points -- built with -fsanitize=address,undefined and run (tests/san/)."""
+    the oracle's double-precision entry points, and the options of a field launch with their environment switches (hn_launch_opts.h) --
+    built with -fsanitize=address,undefined and run (tests/san/)."""
     import subprocess
     san = os.path.join(ROOT, 'tests', 'san')
     subprocess.check_call(['make', '-C', san, '-s'], stdout=subprocess.DEVNULL)
     env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=0', UBSAN_OPTIONS='print_stacktrace=1:halt_on_error=1')
-    for exe, ok in (('pose_chain_san', 'pose chain: ok'), ('pack_layout_san', 'pack layout: ok')):
+    for exe, ok in (('pose_chain_san', 'pose chain: ok'), ('pack_layout_san', 'pack layout: ok'), ('launch_opts_san', 'launch opts: ok')):
         r = subprocess.run([os.path.join(san, '_build', exe)], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0 and ok in r.stdout and 'Sanitizer' not in r.stderr and 'runtime error' not in r.stderr, \
             '%s: rc %d\n%s\n%s' % (exe, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
