@@ -847,6 +847,46 @@ int hn_meshcast_prepare(const float* vertices, long long n_verts, const long lon
 int hn_meshcast(const void* workspace, size_t workspace_bytes, long long n_tris, const float* rays_o, const float* rays_d, long long n_rays, float near,
                 float far, int cull, float* t, int* face, float* bary, float* normal, hn_stream_t stream);
 
+/* ---- connected components of a triangle mesh (hn_meshcc.hip): label, measure, keep -- Trimesh.split / .area / .volume on the device --
+ * The rule.  Two triangles belong to the same component when they share a vertex index, transitively: vertex
+ * connectivity (trimesh's split joins over shared edges; the two differ only at pinch vertices).  A component's label is the smallest
+ * vertex index any of its triangles uses; vertex_label[v] is that label, -1 for a vertex no triangle uses; face_label[f] is the label of
+ * its vertices.  A triangle with a repeated index is a face like any other; a triangle with an index outside [0, n_verts) is never
+ * dereferenced, joins nothing and gets -1 (hn_meshcast_prepare's rule).  Components are numbered 0 .. C-1 in ascending label order (the
+ * component index); vertex_component / face_component carry it (-1 as above).  Every output is the same bits on every run.
+ * Triangles are int64 [n_tris, 3]; vertices [n_verts, 3] fp32 (vertices_f64 = 0) or fp64 (1); labels, components and maps int32.
+ *   hn_meshcc_workspace_bytes: the workspace of hn_meshcc_label and of the two compaction calls (0 for refused counts);
+ *   hn_meshcc_measure_workspace_bytes: the workspace of hn_meshcc_measure for n_comp components (0 for refused counts);
+ *   hn_meshcc_label: a lock-free union-find over the vertices (links only from the larger root to the smaller, agent-scope atomics),
+ *     flattened in a launch of its own, then the roots ranked by count / scan / emit -> vertex_label, vertex_component [n_verts],
+ *     face_label, face_component [n_tris], label [n_verts] (its first C entries: the label of component i), total [1] int64 DEVICE = C
+ *     (the caller reads it back);
+ *   hn_meshcc_measure: face_order [n_tris] int64 lists the faces by component, each component's in ascending face order (a stable sort
+ *     of face_component; faces of no component first) -> faces, vertices_used [n_comp] int64 (integer atomics), area, volume [n_comp]
+ *     fp64, bounds [n_comp, 6] in the vertices' precision (min xyz, max xyz of the used vertices).  Per face, from the vertices
+ *     converted to fp64: area 0.5 |(b - a) x (c - a)|, volume a . (b x c) / 6 (signed: positive for an outward closed surface).  A
+ *     component's sums run over its faces in face_order with a fixed tree (chunks of 256 faces, then the chunks in order): no float
+ *     atomics, the bits depend on the mesh alone;
+ *   hn_meshcc_compact_count: keep [n_comp] uint8 -> totals [2] int64 DEVICE = {V', T'}: the vertices and faces whose component is kept;
+ *   hn_meshcc_compact_emit: on the workspace of the count call with the same arguments (same stream) -> vertices_out [n_verts_out, 3]
+ *     (rows copied bit for bit) and triangles_out [n_tris_out, 3] int64 (re-indexed), both in their original order; vertex_map [n_verts]
+ *     and face_map [n_tris]: the new index, or -1.
+ * Nothing allocates or synchronises.  A NULL input, a negative count, a count >= 2^31 - 256 or a workspace that is too small is HN_EINVAL
+ * with a message, before anything is launched; n_tris = 0 launches nothing and returns 0 (the outputs are left as they are). */
+size_t hn_meshcc_workspace_bytes(long long n_verts, long long n_tris);
+size_t hn_meshcc_measure_workspace_bytes(long long n_tris, long long n_comp);
+int hn_meshcc_label(const long long* triangles, long long n_verts, long long n_tris, int* vertex_label, int* face_label, int* vertex_component,
+                    int* face_component, int* label, long long* total, void* workspace, size_t workspace_bytes, hn_stream_t stream);
+int hn_meshcc_measure(const void* vertices, int vertices_f64, long long n_verts, const long long* triangles, long long n_tris, const int* vertex_component,
+                      const int* face_component, const long long* face_order, long long n_comp, long long* faces, long long* vertices_used, double* area,
+                      double* volume, void* bounds, void* workspace, size_t workspace_bytes, hn_stream_t stream);
+int hn_meshcc_compact_count(const int* vertex_component, long long n_verts, const int* face_component, long long n_tris, const unsigned char* keep,
+                            long long n_comp, long long* totals, void* workspace, size_t workspace_bytes, hn_stream_t stream);
+int hn_meshcc_compact_emit(const void* vertices, int vertices_f64, long long n_verts, const long long* triangles, long long n_tris,
+                           const int* vertex_component, const int* face_component, const unsigned char* keep, long long n_comp, const void* workspace,
+                           size_t workspace_bytes, long long n_verts_out, long long n_tris_out, void* vertices_out, long long* triangles_out,
+                           int* vertex_map, int* face_map, hn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
