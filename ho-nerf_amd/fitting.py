@@ -838,6 +838,9 @@ class PoseAdam:
             sizes[i], lrs[i], steps[i] = p.numel(), lr, st[2]
         L.check(L.load().hn_adam_step(n, P, G, M, V, sizes, lrs, self.betas[0], self.betas[1], self.eps, steps,
                                       L.stream_ptr() if stream is None else stream), 'hn_adam_step')
+        # the launch wrote the parameters through raw pointers: advance their version counters, as an in-place torch update would
+        # have, so that everything keyed on nets.params_version() (a module's own packed copy, the renderers' fields) re-packs
+        torch.autograd.graph.increment_version([p for p, _ in todo])
 
 
 class PipelinedSingleFit:

@@ -267,7 +267,8 @@ int hn_nearest_masked(const float* pts, int n_verts, int n_sets, const unsigned 
  * PoseConverter.get_refine_3d_joint / rot6d_to_matrix / PoseConverter.forward (halo_util/converter_fit_batch.py:103-162,
  * 1109-1229; halo_util/utils.py:17-41; utils/utils.py:11-30) in one launch instead of ~4 000 torch operators.
  *   ori_pose [F,21,3]  the predicted joints, MANO order (ori_3d_pose);  bone_len [F,20]  cur_bone_length;
- *   is_right [F] bytes or NULL (all right hands, as the fitting scripts pass);
+ *   is_right [F] bytes, one per frame: 0 a left hand, ANY non-zero byte a right hand; or NULL (all right hands, as the
+ *   fitting scripts pass);
  *   params [F,36] = [joint_refine_angle 20 | palm_refine_angle 7 | palm_rot_refine 6 (row-major [3][2]) | palm_trans_refine 3]
  *   -> bt_inv [F,21,4,4] (bone_transformation_inv), joint_3d [F,21,3] (the refined joints, MANO order: the joint loss's
  *   input), and, when jac != NULL, jac [F,399,36] = d [bt_inv | joint_3d] / d params (forward-mode, exact).
@@ -287,7 +288,10 @@ int hn_pose_chain_bwd(const float* jac, const float* g_bt_inv, const float* g_jo
  *   bt_inv0 [F,21,4,4], joints0 [F,21,3] (used when with_palm != 0), Ro_pred [F,3,3], To_pred [F,3] ->
  *   out [F,412] = [bt_inv 336 = bt_inv0 G^-1 | joint_3d 63 = G joints0 | obj_r 9 = rot6d(obj_rot) Ro_pred | obj_t 3 |
  *   joint loss 1 = sum_j |joints0_j - joint_3d_j| / 21] with G p = R_palm (p - root) + root + T_palm, and, when jac != NULL,
- *   jac [F,412,18].  with_palm == 0: the object half only (entries 399 .. 410 of out / jac are written).
+ *   jac [F,412,18].  with_palm == 0: the object half only: entries 399 .. 410 of out and rows 399 .. 410 of jac (all 18
+ *   columns; columns 9 .. 17 are zeros) are written, the same bits as with_palm != 0 writes there; entries 0 .. 398 and 411 of
+ *   out and those rows of jac are left untouched, and bt_inv0 / joints0 are not read (they may be NULL).  jac == NULL: the
+ *   values alone, the same bits.
  * hn_verts_loss: pose_loss between the vertex sets of two rigid poses, loss[p] = mean_v |(Ra - Rb) v + (ta - tb)|, with
  *   its gradient w.r.t. (Ra, ta) (the gradient w.r.t. (Rb, tb) is its negative): Ra, Rb [P,3,3], ta, tb [P,3], verts [V,3].
  * hn_jacobian_vjp: out [F,n_in] = jac[F,n_out,n_in]^T g [F,n_out] (n_in <= 64): the backward pass of a dual-number op. */

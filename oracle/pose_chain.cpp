@@ -3,8 +3,8 @@
 // halo_util functions it calls, ho-nerf_amd/csrc/hn_pose_chain.h (every function cites its reference lines), compiled
 // here for the host in double precision; the device kernel instantiates the same header in float.  Because the two share
 // that header, agreement between them says nothing about the restatement itself: both are pinned against
-// tests/golden/pose_chain.npz -- values, refined joints and the full Jacobian obtained by executing the reference's own
-// statements under autograd (tests/golden/make_golden.py, pose_goldens).
+// tests/golden/pose_chain.npz (right hands) and pose_chain_left.npz (left hands) -- values, refined joints and the full
+// Jacobian obtained by executing the reference's own statements under autograd (tests/golden/make_golden.py, pose_goldens).
 //   g++ -O2 -shared -fPIC -I ../ho-nerf_amd/csrc pose_chain.cpp -o _build/libpose_chain_oracle.so   (oracle/Makefile)
 #include "hn_pose_chain.h"
 
@@ -13,8 +13,8 @@ using hn::pose::N_IN;
 using hn::pose::N_OUT;
 
 // the per-finger form of the chain (what the device kernel runs) against the whole-hand form: max |difference| over all
-// outputs and directions of the given frames
-extern "C" double oracle_pose_chain_forms_differ(const double* ori_pose, const double* bone_len, const double* params, int n_frames) {
+// outputs and directions of the given frames (is_right: one flag for all of them, 0 = left hands)
+extern "C" double oracle_pose_chain_forms_differ(const double* ori_pose, const double* bone_len, int is_right, const double* params, int n_frames) {
     double worst = 0.0;
     for (int f = 0; f < n_frames; ++f) {
         double pose[21][3], bl[20];
@@ -23,8 +23,8 @@ extern "C" double oracle_pose_chain_forms_differ(const double* ori_pose, const d
         for (int k = 0; k <= N_IN; ++k) {
             Dual<double> x[N_IN], y[N_OUT], z[N_OUT];
             for (int i = 0; i < N_IN; ++i) x[i] = Dual<double>(params[f * N_IN + i], i == k - 1 ? 1.0 : 0.0);
-            hn::pose::pose_chain<double>(pose, bl, true, x, y);
-            hn::pose::pose_chain_by_finger<double>(pose, bl, true, x, z);
+            hn::pose::pose_chain<double>(pose, bl, is_right != 0, x, y);
+            hn::pose::pose_chain_by_finger<double>(pose, bl, is_right != 0, x, z);
             for (int i = 0; i < N_OUT; ++i) {
                 const double dv = y[i].v - z[i].v, dd = y[i].d - z[i].d;
                 if (dv < 0 ? -dv > worst : dv > worst) worst = dv < 0 ? -dv : dv;

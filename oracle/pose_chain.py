@@ -19,6 +19,8 @@ def _load():
         dp = ctypes.POINTER(ctypes.c_double)
         _lib.oracle_pose_chain.restype = ctypes.c_int
         _lib.oracle_pose_chain.argtypes = [dp, dp, ctypes.c_int, dp, ctypes.c_int, dp, dp, dp]
+        _lib.oracle_pose_chain_forms_differ.restype = ctypes.c_double
+        _lib.oracle_pose_chain_forms_differ.argtypes = [dp, dp, ctypes.c_int, dp, ctypes.c_int]
     return _lib
 
 
@@ -38,3 +40,16 @@ def pose_chain(ori_pose, bone_len, params, is_right=True, want_jac=True):
     rc = lib.oracle_pose_chain(q(a), q(b), 1 if is_right else 0, q(p), F, q(bt), q(j3), q(jac))
     assert rc == 0
     return bt, j3, jac
+
+
+def pose_chain_forms_differ(ori_pose, bone_len, params, is_right=True):
+    """max |difference|, over every output and every input direction of the given frames, between the chain's per-finger
+    form (what the device kernel runs) and its whole-hand form."""
+    lib = _load()
+    a = np.ascontiguousarray(ori_pose, dtype=np.float64).reshape(-1, 21, 3)
+    b = np.ascontiguousarray(bone_len, dtype=np.float64).reshape(-1, 20)
+    p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 36)
+    assert b.shape[0] == a.shape[0] and p.shape[0] == a.shape[0]
+    dp = ctypes.POINTER(ctypes.c_double)
+    q = lambda x: x.ctypes.data_as(dp)
+    return float(lib.oracle_pose_chain_forms_differ(q(a), q(b), 1 if is_right else 0, q(p), a.shape[0]))

@@ -166,17 +166,19 @@ def hand_scene_rays(n, seed):
     return o, d, torch.from_numpy(bt_inv), torch.from_numpy(T_pose), joints
 
 
-def reference_block(path, start_marker, end_marker):
+def reference_block(path, start_marker, end_marker, edit=None):
     """The statements of a reference entry script between two marker lines (start inclusive, end exclusive),
     dedented, as a code object.  The fitting scripts cannot be imported (pyhocon, cv2, trimesh, pytorch3d and a CUDA
     device are needed at import time), but their loss formulas are plain torch statements inside `Runner.fitting`:
     they are read from the reference file HERE, at fixture-generation time, and executed unmodified on synthetic
-    tensors -- nothing of them is stored in this repository, only the numbers they produce."""
+    tensors -- nothing of them is stored in this repository, only the numbers they produce.  `edit`: a function applied to
+    the block's text before it is compiled (the left-hand pose fixture sets the block's handedness flags to zero)."""
     import textwrap
     lines = open(os.path.join(REF, path)).read().split('\n')
     a = next(i for i, l in enumerate(lines) if start_marker in l)
     b = next(i for i, l in enumerate(lines) if end_marker in l and i > a)
-    return compile(textwrap.dedent('\n'.join(lines[a:b])), path + ':%d-%d' % (a + 1, b), 'exec')
+    text = textwrap.dedent('\n'.join(lines[a:b]))
+    return compile(text if edit is None else edit(text), path + ':%d-%d' % (a + 1, b), 'exec')
 
 
 def loss_goldens(nets, nets_b, g):
@@ -302,18 +304,33 @@ def loss_goldens(nets, nets_b, g):
     save('loss_video', stable=stable.detach(), **outv)
 
 
-def pose_goldens():
+# the cases of pose_goldens() that the left-hand fixture holds (indices into pose_chain.npz): the initial state, two moderate,
+# one whole-step hand, two large angles, and all six near-degenerate hands
+POSE_LEFT_CASES = (0, 1, 2, 6, 16, 17, 22, 23, 24, 25, 26, 27)
+
+
+def _left_hands(text):
+    """The pose block with its handedness flags (`is_right_one`, all ones in the reference) set to all zeros."""
+    a, b = 'is_right_one = torch.ones(', 'is_right_one = torch.zeros('
+    assert text.count(a) == 2, 'the pose block no longer sets its handedness flag twice'
+    return text.replace(a, b)
+
+
+def pose_goldens(left=False):
     """The hand pose chain of the fitting loops, fitting_single.py:206-226, executed as the reference has it (the
     statements are read from the reference file here and run unmodified; halo_util is imported) on synthetic predicted
     joints: bone_transformation_inv, the refined joints and the full Jacobian w.r.t. the four refine parameters.
     Run in double precision (torch default dtype float64 while the reference's modules are constructed and executed), so
-    that the fixture is the chain's exact value; the fp32 run's distance from it is stored beside it as the noise floor."""
+    that the fixture is the chain's exact value; the fp32 run's distance from it is stored beside it as the noise floor.
+    left: the cases POSE_LEFT_CASES of the same hands as LEFT hands -> pose_chain_left.npz (the block's two handedness flags,
+    all ones in the reference's fitting loop, are set to zeros in the text read from the reference before it is compiled;
+    pose_chain.npz is not written)."""
     import types as _t
     import torch.nn.functional as F_
     from halo_util.converter_fit_batch import PoseConverter, transform_to_canonical
     from halo_util.utils import convert_joints
     blk = reference_block('fitting_single.py', "kps_local_cs = convert_joints(ori_3d_pose, source='mano', target='biomech')",
-                          'obj_rots = rot6d_to_matrix(obj_rot_refine)')
+                          'obj_rots = rot6d_to_matrix(obj_rot_refine)', edit=_left_hands if left else None)
     r6 = reference_block('utils/utils.py', 'def rot6d_to_matrix(rot_6d)', 'def _xy_to_ray_bundle')
     m2b = np.array([0, 1, 5, 9, 13, 17, 2, 6, 10, 14, 18, 3, 7, 11, 15, 19, 4, 8, 12, 16, 20])   # halo_util/utils.py:20
 
@@ -344,6 +361,11 @@ def pose_goldens():
     rng = np.random.RandomState(2024)
     N = 6
     oris, bls, prms, outs, jacs, floor = [], [], [], [], [], []
+    case = [0]                  # index of the next case among all of pose_goldens()'s (the inputs of every case are drawn either way)
+
+    def wanted():
+        case[0] += 1
+        return not left or case[0] - 1 in POSE_LEFT_CASES
     for c in range(N):
         _, _, joints = synth.synth_hand_pose(100 + c, center=(0.01 * c, -0.02, 0.9), flex=0.3 + 0.05 * c)
         joints = joints.astype(np.float64) + 0.004 * rng.standard_normal((21, 3))       # off the synthetic hand's plane
@@ -356,6 +378,8 @@ def pose_goldens():
             prm[20:27] = 0.3 * rng.standard_normal(7)
             prm[27:33] += 0.15 * rng.standard_normal(6)
             prm[33:36] = 0.01 * rng.standard_normal(3)
+        if not wanted():
+            continue
         o64, j64 = run(torch.float64, joints, bl, prm, True)
         o32, _ = run(torch.float32, joints, bl, prm, False)
         oris.append(joints); bls.append(bl); prms.append(prm); outs.append(o64); jacs.append(j64)
@@ -363,10 +387,12 @@ def pose_goldens():
         print('pose chain case %d: |out| max %.3f, fp32 run vs fp64 run %.2e, |jac| max %.3f' % (c, np.abs(o64).max(), floor[-1], np.abs(j64).max()))
     # ---- round 5: 24 more hands, so that the chain is pinned WHERE IT IS USED and away from the easy middle.
     # Cases 0 .. 5 above are unchanged (same generator stream).  `kinds` names every case in the fixture.
-    kinds = ['initial state'] + ['moderate refinements'] * 5
+    kinds = ['initial state'] + ['moderate refinements'] * (len(oris) - 1)
     rng2 = np.random.RandomState(2025)
 
     def add(kind, joints, bl, prm):
+        if not wanted():
+            return
         o64, j64 = run(torch.float64, joints, bl, prm, True)
         o32, _ = run(torch.float32, joints, bl, prm, False)
         if not (np.isfinite(o64).all() and np.isfinite(j64).all()):
@@ -441,6 +467,12 @@ def pose_goldens():
         add('bench sequence frame %d' % f, jj, bone_lengths_of(jj.astype(np.float32)[None])[0].numpy().astype(np.float64), prm)
     N = len(oris)
     outs = np.stack(outs)
+    if left:
+        assert N == len(POSE_LEFT_CASES), 'the reference was not finite on a left-hand case'
+        save('pose_chain_left', ori_pose=np.stack(oris), bone_len=np.stack(bls), params=np.stack(prms), bt_inv=outs[:, :336].reshape(N, 21, 4, 4),
+             joint_3d=outs[:, 336:].reshape(N, 21, 3), jac=np.stack(jacs), ref32_vs_ref64=np.array(floor), kinds=np.array(kinds),
+             is_right=np.zeros(N, dtype=np.uint8), case_of_pose_chain=np.array(POSE_LEFT_CASES))
+        return
     save('pose_chain', ori_pose=np.stack(oris), bone_len=np.stack(bls), params=np.stack(prms), bt_inv=outs[:, :336].reshape(N, 21, 4, 4),
          joint_3d=outs[:, 336:].reshape(N, 21, 3), jac=np.stack(jacs), ref32_vs_ref64=np.array(floor), kinds=np.array(kinds))
 
@@ -449,6 +481,9 @@ def main():
     only = os.environ.get('HONERF_GOLDEN_ONLY', '')
     if only == 'pose':
         pose_goldens()
+        return
+    if only == 'pose_left':
+        pose_goldens(left=True)
         return
     if only == 'loss':
         emb, nets = build_nets()

@@ -7,7 +7,7 @@
 
 #include <vector>
 
-extern "C" double oracle_pose_chain_forms_differ(const double*, const double*, const double*, int);
+extern "C" double oracle_pose_chain_forms_differ(const double*, const double*, int, const double*, int);
 extern "C" int oracle_pose_chain(const double*, const double*, int, const double*, int, double*, double*, double*);
 
 int main() {
@@ -39,7 +39,13 @@ int main() {
     for (double v : bt) bad += !std::isfinite(v);
     for (double v : j3) bad += !std::isfinite(v);
     for (double v : jac) bad += !std::isfinite(v);
-    const double d = oracle_pose_chain_forms_differ(pose.data(), bl.data(), prm.data(), F);
+    double d = oracle_pose_chain_forms_differ(pose.data(), bl.data(), 1, prm.data(), F);
+    // the same hands as left hands: the !is_right branches of the header
+    if (oracle_pose_chain(pose.data(), bl.data(), 0, prm.data(), F, bt.data(), j3.data(), jac.data()) != 0) return 2;
+    for (double v : bt) bad += !std::isfinite(v);
+    for (double v : j3) bad += !std::isfinite(v);
+    for (double v : jac) bad += !std::isfinite(v);
+    d = fmax(d, oracle_pose_chain_forms_differ(pose.data(), bl.data(), 0, prm.data(), F));
     printf("pose chain: %d non-finite outputs; per-finger form vs whole-hand form: max |difference| %.3e\n", bad, d);
     if (bad || !(d < 1e-9)) {
         printf("FAILED\n");
