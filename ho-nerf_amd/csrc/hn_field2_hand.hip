@@ -40,6 +40,11 @@
 #define HN_FAR_TILES 1
 #endif
 #endif
+#ifndef HN_DBG_FAR_NO_EPILOGUE
+#define HN_DBG_FAR_NO_EPILOGUE 0   // 1 (measurement only, WRONG results): the all-far program's 15 SDF-side tile epilogues (lin0..lin7, the seven
+                                   // layers of the reverse sweep) issue no phase work: the next layer's fragments are conversions of the raw
+                                   // accumulators and a_l is not read back -- an upper bound on what the shared epilogue can buy (profiles/r11)
+#endif
 #ifndef HN_DEFER_STASH
 #define HN_DEFER_STASH 0   // 1: the fp32 activation tiles of the hidden layers go to the stash one chunk late (to_regs_hold): measured, no gain
 #endif
@@ -78,6 +83,8 @@ struct Hand2Args {
                 // form -- StashT::ush in its low four bits (USTASH_SHIFT); 0 = off
     int far_tiles;   // HONERF_FAR_TILES (FieldLaunchOpts::far_tiles) and the packed uniform stash, the full evaluation (MODE 1) only: a tile
                      // whose four waves are all far runs the all-far tile program (FarStash below); 0 = every tile runs the general one
+    int far_epilogue;   // HONERF_FAR_EPILOGUE (FieldLaunchOpts::far_epilogue): the all-far program computes the SDF layers' element-wise
+                        // epilogues once per row of lanes (PhFarShared below); 0 = per lane, as the general program does
     // adjoint (MODE 2): upstream gradients in, input / pose gradients out
     const float* g_sdf;    // [n]
     const float* g_grad;   // [n,3]
@@ -165,14 +172,33 @@ constexpr size_t HAND2_LDS_POSE = 2 * CHUNK_MAX + WG_WAVES * STAGE_BYTES + 16;  
 constexpr int FAR_IMAGE_BYTES = (HS_DZ4 + 1) * (SLOT_BYTES >> USTASH_SHIFT);
 static_assert(HS_A1 == 0 && HS_DZ7 == 7 && HS_FVEC == 8 && HS_DZ4 == 9 && FAR_IMAGE_BYTES == 10240 && HAND2_LDS_POSE % 16 == 0 && STAGE_BYTES >= 1024,
               "the all-far image covers the slots 0 .. HS_DZ4 and its stores' dump is the wave's staging area");
-constexpr size_t HAND2_LDS_EVAL = HAND2_LDS_POSE + WG_WAVES * FAR_IMAGE_BYTES;   // the full evaluation kernels' LDS (they keep no pose rows)
+// Behind each wave's image: the two lines of the shared epilogue (PhFarShared below) -- FAR_Z, the 32 fp32 results of one output tile
+// of lin7 (a8 has no slot in the image) in the layout of an image tile ([block q][half][4 floats]: register i of half h at
+// 32 (i >> 2) + 16 h + 4 (i & 3)), and FAR_FRAG, the tile's four B fragments per half ([half][hi 0 | hi 1 | lo 0 | lo 1], 16 bytes each: element i's hi part at 64 h + 2 i, its lo part
+// 32 bytes on -- frag_u(i) = i >> 3, frag_j(i) = i & 7 on this shape).
+constexpr int FAR_Z = FAR_IMAGE_BYTES;
+constexpr int FAR_FRAG = FAR_IMAGE_BYTES + 128;
+constexpr int FAR_WAVE_BYTES = FAR_IMAGE_BYTES + 256;
+constexpr size_t HAND2_LDS_EVAL = HAND2_LDS_POSE + WG_WAVES * FAR_WAVE_BYTES;   // the full evaluation kernels' LDS (they keep no pose rows)
 static_assert(HAND2_LDS_EVAL <= 160 * 1024, "LDS of a CU");
+static_assert(S16 || (frag_u(9) == 1 && frag_j(9) == 1 && frag_u(7) == 0 && frag_j(7) == 7), "FAR_FRAG's element map is the 32x32x16 shape's");
 struct FarStash {
     char* img;    // this wave's image
     char* dump;   // 1 KiB that nobody reads
     __device__ __forceinline__ void init(char* lds, int wave) {
-        img = lds + HAND2_LDS_POSE + wave * FAR_IMAGE_BYTES;
+        img = lds + HAND2_LDS_POSE + wave * FAR_WAVE_BYTES;
         dump = lds + 2 * CHUNK_MAX + wave * STAGE_BYTES;
+    }
+    // the 16 values of this lane's half of the line FAR_Z (lin7's a8 under the shared epilogue), as tile_load reads an image tile
+    __device__ __forceinline__ void line_load(float (&v)[16]) const {
+        using f32x4 = float __attribute__((ext_vector_type(4)));
+        const char* const p = img + FAR_Z + ((lane_x16() & 512) >> USTASH_SHIFT);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 x = *reinterpret_cast<const f32x4*>(p + 32 * q);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[4 * q + i] = x[i];
+        }
     }
     // where this lane stores its 16 bytes of the block at byte offset `off` (a multiple of 1 KiB) of the wave's region
     __device__ __forceinline__ char* st_at(int off) const {
@@ -213,6 +239,107 @@ struct FarStash {
         const char* const p = ld_at(base + s * KS_BYTES);
         hi = *reinterpret_cast<const h8*>(p);
         lo = *reinterpret_cast<const h8*>(p + (1024 >> USTASH_SHIFT));
+    }
+};
+
+// ---- the shared epilogue of the all-far program (HONERF_FAR_EPILOGUE, Hand2Args::far_epilogue) ---------------------------------------
+// In an all-far tile the 16 values that lane (j, h) holds of an output tile do not depend on j, so the element-wise epilogue of the SDF
+// network's layers (softplus forward, g sigma' in the reverse sweep) and the fp16 split behind it are the same 32 results computed by
+// 32 lanes each.  Here they are computed ONCE per row of 16 lanes, one element per lane, and come back to every lane through LDS:
+//   calls 0..7   every lane forms z = c2 * inv + c1, the packed fma of pair_phase, and keeps element e = j & 15 of the 16: a tree of 15
+//                v_cndmask_b32 on the four low bits of the lane number, the masks being constants in scalar registers (the first form
+//                sent z through LDS -- the j == 0 lanes stored a line of 16 z per half, every lane read one element back: four
+//                ds_write_b128 of the whole wave per tile, and the reverse sweep came out SLOWER than per lane in the in-kernel stamps);
+//   call 10      KIND 1: lane (j, h) reads element e of a_l straight from the image;
+//   calls 16..19 one element through pair_phase's operations in scalar form (v_mul, v_exp, v_add, v_log, v_max, v_fma: the packed
+//                forms round each half as these do);
+//   call 20      the fp32 result to the image cell where tile_store would have put it (DST: an a_l slot; the lanes j and j ^ 16
+//                store the same bits to the same cell), or back to FAR_Z (DST_LINE: lin7, whose `fin` reads all 16);
+//   calls 21, 22 split_pair_hi / split_pair_lo's instructions on the one value, the two halves to FAR_FRAG;
+//   call 28      every lane reads the tile's four fragments, four broadcast ds_read_b128.
+// A wave's LDS operations complete in order, so nothing but program order stands between a line's store and its read.  The calls sit
+// in the MFMA slots of the next tile like pair_phase's (Epi::run); the lane offsets are formed where they are used (lane_x16()).
+// pd.t is the tile's index within the layer.
+struct FarTile {
+    int t;
+};
+struct FarActT {
+    f32x16 v;
+    int t;
+};
+constexpr int DST_NONE = -1, DST_LINE = -2;
+// lane bit B set ? b : a -- one v_cndmask_b32 whose mask is a constant (no v_cmp, nothing live across the tile)
+template <int B>
+__device__ __forceinline__ float lane_bit_select(float a, float b) {
+    constexpr unsigned long long M = B == 0 ? 0xAAAAAAAAAAAAAAAAull : (B == 1 ? 0xCCCCCCCCCCCCCCCCull : (B == 2 ? 0xF0F0F0F0F0F0F0F0ull : 0xFF00FF00FF00FF00ull));
+    float r;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(M));
+    return r;
+}
+template <int KIND, int DST, int ACT>   // KIND: 0 softplus, 1 PhDsig; DST: slot of the fp32 results; ACT (KIND 1): slot of a_l
+struct PhFarShared {
+    static_assert(KIND == 0 || KIND == 1, "softplus or g sigma'");
+    static constexpr bool own_calls = true;
+    static constexpr int kind = KIND;
+    static constexpr bool branchy = KIND == 0 ? HN_BRANCHY_FWD : HN_BRANCHY_REV;
+    char* img;
+    float z, x, v;       // carried from call to call of one tile
+    float g[8];          // the select tree of calls 0..7
+    unsigned hp, lp;
+    char* pe;
+    template <int C, bool FRAGS, typename PD>
+    __device__ __forceinline__ void call(EpiState& st, const PD& pd) {
+        if constexpr (C < 8) {
+            constexpr int i0 = 2 * C, i1 = 2 * C + 1;
+            const f32x2 c1 = {st.c1[i0], st.c1[i1]}, c2 = {st.c2[i0], st.c2[i1]};
+            const f32x2 inv = {st.inv, st.inv};
+            const f32x2 z2 = c2 * inv + c1;
+            g[C] = lane_bit_select<0>(z2[0], z2[1]);
+            if constexpr ((C & 1) == 1) g[C - 1] = lane_bit_select<1>(g[C - 1], g[C]);
+            if constexpr ((C & 3) == 3) g[C - 3] = lane_bit_select<2>(g[C - 3], g[C - 1]);
+            if constexpr (C == 7) z = lane_bit_select<3>(g[0], g[4]);
+        } else if constexpr (C == 10) {
+            const int l16 = lane_x16();   // 512 h + 16 j -> 32 (e >> 2) + 16 h + 4 (e & 3), e = j & 15
+            pe = img + (((l16 & 0xC0) >> 1) | ((l16 >> 5) & 16) | ((l16 >> 2) & 12));
+            if constexpr (KIND == 1) x = *reinterpret_cast<const float*>(pe + (ACT * SLOT_BYTES >> USTASH_SHIFT) + pd.t * 128);
+        } else if constexpr (C == 16) {
+            x = KIND == 0 ? z * K100_ : x * -K100_;
+        } else if constexpr (C == 17) {
+            x = KIND == 0 ? __builtin_amdgcn_exp2f(-fabsf(x)) : __builtin_amdgcn_exp2f(x);
+        } else if constexpr (C == 18) {
+            if constexpr (KIND == 0) x = __builtin_amdgcn_logf(x + 1.f);
+        } else if constexpr (C == 19) {
+            if constexpr (KIND == 0)
+                v = x * C100_ + fmaxf(z, 0.f);
+            else
+                v = z - z * x;
+        } else if constexpr (C == 20) {
+            if constexpr (DST == DST_LINE) *reinterpret_cast<float*>(pe + FAR_Z) = v;
+            if constexpr (DST >= 0) *reinterpret_cast<float*>(pe + (DST * SLOT_BYTES >> USTASH_SHIFT) + pd.t * 128) = v;
+        } else if constexpr (C == 21) {
+            if constexpr (FRAGS) {
+                float r;   // (the instructions of split_pair_hi / split_pair_lo, both members of the pair being this value)
+                asm("v_cvt_pk_f16_f32 %0, %3, %3\n\t"
+                    "v_fma_mix_f32 %1, %0, -1.0, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
+                    "v_fma_mixlo_f16 %2, %1, %4, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]"
+                    : "=&v"(hp), "=&v"(r), "=&v"(lp)
+                    : "v"(v), "v"(st.scale));
+            }
+        } else if constexpr (C == 22) {
+            if constexpr (FRAGS) {
+                char* const p = img + FAR_FRAG + ((lane_x16() >> 3) & 94);   // 64 h + 2 (j & 15)
+                *reinterpret_cast<unsigned short*>(p) = (unsigned short)hp;
+                *reinterpret_cast<unsigned short*>(p + 32) = (unsigned short)lp;
+            }
+        } else if constexpr (C == 28) {
+            if constexpr (FRAGS) {
+                const char* const p = img + FAR_FRAG + ((lane_x16() >> 3) & 64);
+                st.hi[0] = *reinterpret_cast<const h8*>(p);
+                st.hi[1] = *reinterpret_cast<const h8*>(p + 16);
+                st.lo[0] = *reinterpret_cast<const h8*>(p + 32);
+                st.lo[1] = *reinterpret_cast<const h8*>(p + 48);
+            }
+        }
     }
 };
 
@@ -638,8 +765,13 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             far = nz_any == 0u && a.cull == 0 && a.far_tiles != 0;
         }
         // the tile program from here on: FAR_ = the all-far instance (returns true where a phase-timing build leaves the kernel)
+        // (FAR_ = 2: the all-far instance with the shared epilogue, PhFarShared)
         auto program = [&](auto FAR_) __attribute__((always_inline)) -> bool {
-        constexpr bool FAR = decltype(FAR_)::value;
+        constexpr bool FAR = decltype(FAR_)::value != 0;
+        constexpr bool SH = decltype(FAR_)::value == 2;
+        constexpr bool RAW = FAR && HN_DBG_FAR_NO_EPILOGUE;   // (measurement build)
+        using PhSp = std::conditional_t<RAW, PhRaw, PhSoftplus>;
+        using PhDs = std::conditional_t<RAW, PhRaw, PhDsig>;
         const unsigned nz = FAR ? 0u : nz_w;
         unsigned nzw = FAR ? (1u << N_BONES) - 1u : nzw_w;
         auto& sh = [&]() -> auto& {
@@ -937,6 +1069,23 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 fin(std::integral_constant<int, ti>{}, st, nd);
             });
         };
+        // the same under the shared epilogue: the phase type gets the tile's index
+        [[maybe_unused]] auto block_epilogue_far = [&](auto NT_, auto& c1, auto& c2, auto&& ph, auto&& fin) {
+            constexpr int NTT = decltype(NT_)::value;
+            static_for<NTT>([&](auto TI) {
+                constexpr int ti = decltype(TI)::value;
+                EpiState st;
+                arm(st);
+                st.c1 = c1[ti];
+                st.c2 = c2[ti];
+                const FarTile ft{ti};
+                Epi<true, std::remove_reference_t<decltype(ph)>, FarTile> epi{st, ph, ft};
+                epi.run_all();
+                split_finish<true>(st);
+                fin(std::integral_constant<int, ti>{}, st, ft);
+            });
+        };
+        [[maybe_unused]] auto far_pre = [](auto T, const char*) { return FarTile{decltype(T)::value}; };
         using I2 = std::integral_constant<int, 2>;
         using I8t = std::integral_constant<int, 8>;
         using BTrue = std::integral_constant<bool, true>;
@@ -960,26 +1109,41 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 c2[ti] = zero16();
             }
             feature_pass(I2{}, BTrue{}, c1, c2, std::integral_constant<int, HB_LEFT_T>{}, std::integral_constant<int, HB_HID>{}, IPF{});
-            block_epilogue(I8t{}, c1, c2, PhSoftplus{}, to_regs_keep(ah, al, HS_A1 + 0));
+            if constexpr (SH)
+                block_epilogue_far(I8t{}, c1, c2, PhFarShared<0, HS_A1 + 0, 0>{shf.img}, to_regs(ah, al));
+            else
+                block_epilogue(I8t{}, c1, c2, PhSp{}, to_regs_keep(ah, al, HS_A1 + 0));
         }
+        if constexpr (SH) {
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, HS_A1 + 1, 0>{shf.img}, to_regs(bh, bl), no_store);   // lin1
+        } else {
 #if HN_DEFER_STASH
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 1));   // lin1
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 1));   // lin1
 #else
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_keep(bh, bl, HS_A1 + 1), no_store);   // lin1
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_keep(bh, bl, HS_A1 + 1), no_store);   // lin1
 #endif
+        }
+        if constexpr (SH) {
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<0, HS_A1 + 2, 0>{shf.img}, to_regs(ah, al), no_store);   // lin2
+        } else {
 #if HN_DEFER_STASH
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSoftplus{}, to_regs_hold(ah, al), store_tile(HS_A1 + 2));   // lin2
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSp{}, to_regs_hold(ah, al), store_tile(HS_A1 + 2));   // lin2
 #else
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSoftplus{}, to_regs_keep(ah, al, HS_A1 + 2), no_store);   // lin2
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSp{}, to_regs_keep(ah, al, HS_A1 + 2), no_store);   // lin2
 #endif
+        }
         // lin3 -> a4, in bh / bl like every layer's output: lin4's hidden part reads them from there.  (They used to go
         // through the stash -- 32 KB written and read back at once per tile, an HBM round trip of ~10 000 cycles in front
         // of lin4 in the in-kernel stamps.)
+        if constexpr (SH) {
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, HS_A1 + 3, 0>{shf.img}, to_regs(bh, bl), no_store);   // lin3
+        } else {
 #if HN_DEFER_STASH
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 3));   // lin3
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 3));   // lin3
 #else
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_keep(bh, bl, HS_A1 + 3), no_store);   // lin3
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_keep(bh, bl, HS_A1 + 3), no_store);   // lin3
 #endif
+        }
         if ((HN_DBG(a) >> 8) == 3) return true;   // phase timing aid
         // ---- lin4 = [a4 | features] / sqrt2 -> a5: 8 hidden tiles (bias from the tail), then the feature pass
         {
@@ -994,27 +1158,52 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 mma_tile<16, 0, nbytes, PH>(ws, buf, bh, bl, c1[ti], c2[ti], lane);
             });
             feature_pass(I2{}, BFalse{}, c1, c2, std::integral_constant<int, HB_LEFT>{}, std::integral_constant<int, HB_HID>{}, IPF{});
-            block_epilogue(I8t{}, c1, c2, PhSoftplus{}, to_regs_keep(ah, al, HS_A1 + 4));
+            if constexpr (SH)
+                block_epilogue_far(I8t{}, c1, c2, PhFarShared<0, HS_A1 + 4, 0>{shf.img}, to_regs(ah, al));
+            else
+                block_epilogue(I8t{}, c1, c2, PhSp{}, to_regs_keep(ah, al, HS_A1 + 4));
         }
+        if constexpr (SH) {
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, HS_A1 + 5, 0>{shf.img}, to_regs(bh, bl), no_store);   // lin5
+        } else {
 #if HN_DEFER_STASH
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 5));   // lin5
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 5));   // lin5
 #else
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSoftplus{}, to_regs_keep(bh, bl, HS_A1 + 5), no_store);   // lin5
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_keep(bh, bl, HS_A1 + 5), no_store);   // lin5
 #endif
+        }
+        if constexpr (SH) {
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<0, HS_A1 + 6, 0>{shf.img}, to_regs(ah, al), no_store);   // lin6
+        } else {
 #if HN_DEFER_STASH
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSoftplus{}, to_regs_hold(ah, al), store_tile(HS_A1 + 6));   // lin6
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSp{}, to_regs_hold(ah, al), store_tile(HS_A1 + 6));   // lin6
 #else
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSoftplus{}, to_regs_keep(ah, al, HS_A1 + 6), no_store);   // lin6
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSp{}, to_regs_keep(ah, al, HS_A1 + 6), no_store);   // lin6
 #endif
+        }
         // ---- lin7 -> a8; sdf = W8[0,:] a8 + b8; seed of the reverse sweep dz7 = sigma'(z7) W8[0,:] (scaled)
         float sdf_acc = 0.f, sdf_acc1 = 0.f;   // (16x16x32: the lane's registers of column block 0 / 1 are two samples)
         auto lin7 = [&](auto NA_) {   // NA_: the size of the chunk that follows the layer, a constant
+        // (the shared epilogue leaves a8's tile in the line FAR_Z: every lane needs its 16 values for the sdf row and the seed)
         run_layer_c<8, 16, 1, true, true, HB_HID, decltype(NA_)::value, P7>(
             ws, ah, al, lane, h,
-            [&](auto, const char* tail) { return Act{tail_tile(tail, 1, h)}; }, PhSoftplus{},
-            [&](auto T, EpiState& st, const Act& w8) {
+            [&](auto T, const char* tail) {
+                (void)T;
+                if constexpr (SH)
+                    return FarActT{tail_tile(tail, 1, h), decltype(T)::value};
+                else
+                    return Act{tail_tile(tail, 1, h)};
+            },
+            [&]() {
+                if constexpr (SH)
+                    return PhFarShared<0, DST_LINE, 0>{shf.img};
+                else
+                    return PhSp{};
+            }(),
+            [&](auto T, EpiState& st, const auto& w8) {
                 constexpr int t = decltype(T)::value;
                 asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
+                if constexpr (SH) shf.line_load(st.v);
                 f32x16 dz;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
@@ -1090,7 +1279,14 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     return Act{sh.tile_load(act_slot, decltype(T)::value)};
             };
 #else
-            return [&sh, act_slot](auto T, const char*) { return Act{sh.tile_load(act_slot, decltype(T)::value)}; };
+            return [&sh, act_slot](auto T, const char*) {
+                (void)sh;
+                (void)act_slot;
+                if constexpr (RAW)
+                    return NoData{};
+                else
+                    return Act{sh.tile_load(act_slot, decltype(T)::value)};
+            };
 #endif
         };
 #pragma unroll
@@ -1111,9 +1307,16 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 return NoData{};
             };
         };
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 6), PhDsig{}, to_regs_t(bh, bl, HS_DZ + 6), no_store);   // W7^T -> dz6
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, act_of(HS_A1 + 5), PhDsig{}, to_regs_t(ah, al, HS_DZ + 5), no_store);   // W6^T -> dz5
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 4), PhDsig{},                               // W5^T -> dz4 (kept)
+        if constexpr (SH)
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 6>{shf.img}, to_regs_t(bh, bl, HS_DZ + 6), no_store);   // W7^T -> dz6
+        else
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 6), PhDs{}, to_regs_t(bh, bl, HS_DZ + 6), no_store);   // W7^T -> dz6
+        if constexpr (SH)
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 5>{shf.img}, to_regs_t(ah, al, HS_DZ + 5), no_store);   // W6^T -> dz5
+        else
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, act_of(HS_A1 + 5), PhDs{}, to_regs_t(ah, al, HS_DZ + 5), no_store);   // W6^T -> dz5
+        auto dz4_layer = [&](auto&& pre4, auto&& ph4) {
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, pre4, ph4,                               // W5^T -> dz4 (kept)
                                          [&](auto T, EpiState& st, const auto&) {
                                              constexpr int t = decltype(T)::value;
                                              asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
@@ -1126,10 +1329,27 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                                              return NoData{};
                                          },
                                          no_store);
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, act_of(HS_A1 + 3), PhDsig{}, to_regs_t(ah, al, HS_DZ + 3), no_store);   // W4h^T -> dz3
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 2), PhDsig{}, to_regs_t(bh, bl, HS_DZ + 2), no_store);   // W3^T -> dz2
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, act_of(HS_A1 + 1), PhDsig{}, to_regs_t(ah, al, HS_DZ + 1), no_store);   // W2^T -> dz1
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 0), PhDsig{}, to_regs_t(bh, bl, HS_DZ + 0), no_store);   // W1^T -> dz0
+        };
+        if constexpr (SH)
+            dz4_layer(far_pre, PhFarShared<1, DST_NONE, HS_A1 + 4>{shf.img});
+        else
+            dz4_layer(act_of(HS_A1 + 4), PhDs{});
+        if constexpr (SH)
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 3>{shf.img}, to_regs_t(ah, al, HS_DZ + 3), no_store);   // W4h^T -> dz3
+        else
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, act_of(HS_A1 + 3), PhDs{}, to_regs_t(ah, al, HS_DZ + 3), no_store);   // W4h^T -> dz3
+        if constexpr (SH)
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 2>{shf.img}, to_regs_t(bh, bl, HS_DZ + 2), no_store);   // W3^T -> dz2
+        else
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 2), PhDs{}, to_regs_t(bh, bl, HS_DZ + 2), no_store);   // W3^T -> dz2
+        if constexpr (SH)
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 1>{shf.img}, to_regs_t(ah, al, HS_DZ + 1), no_store);   // W2^T -> dz1
+        else
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, act_of(HS_A1 + 1), PhDs{}, to_regs_t(ah, al, HS_DZ + 1), no_store);   // W2^T -> dz1
+        if constexpr (SH)
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 0>{shf.img}, to_regs_t(bh, bl, HS_DZ + 0), no_store);   // W1^T -> dz0
+        else
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 0), PhDs{}, to_regs_t(bh, bl, HS_DZ + 0), no_store);   // W1^T -> dz0
 
         if ((HN_DBG(a) >> 8) == 7) return true;   // phase timing aid
         // ---- d sdf / d features contracted with the encoding Jacobian, bone by bone: first W0^T dz0 (dz0 is in
@@ -1387,10 +1607,14 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         }
         return false;
         };   // program
-        if constexpr (FAR_ARM) {
-            if (far ? program(std::true_type{}) : program(std::false_type{})) return;
+        if constexpr (FAR_ARM && !HN_DBG_FAR_NO_EPILOGUE) {
+            const bool out = !far ? program(std::integral_constant<int, 0>{})
+                                  : (a.far_epilogue != 0 ? program(std::integral_constant<int, 2>{}) : program(std::integral_constant<int, 1>{}));
+            if (out) return;
+        } else if constexpr (FAR_ARM) {
+            if (far ? program(std::integral_constant<int, 1>{}) : program(std::integral_constant<int, 0>{})) return;
         } else {
-            if (program(std::false_type{})) return;
+            if (program(std::integral_constant<int, 0>{})) return;
         }
     }
 }
@@ -1565,6 +1789,7 @@ int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const flo
     const int us_mode = full ? lo.uniform_stash : 0;   // (the full evaluation kernels alone are built with it)
     a.ustash = us_mode == 0 ? 0 : (us_mode == 2 ? USTASH_COLS : (USTASH_COLS | USTASH_SHIFT));
     a.far_tiles = (us_mode == 1 && lo.far_tiles != 0) ? 1 : 0;   // (the all-far tile program goes with the default, packed form)
+    a.far_epilogue = lo.far_epilogue != 0 ? 1 : 0;
 #ifdef HN_DEBUG_HOOKS
     {
         const char* e = getenv("HN_DBG");

@@ -25,6 +25,9 @@ struct FieldLaunchOpts {
     // HONERF_FAR_TILES (Hand2Args::far_tiles): 0 = every tile of the hand evaluation kernel runs the general tile program; 1 = all-far
     // tiles run their own (the same bits)
     int far_tiles = 1;
+    // HONERF_FAR_EPILOGUE (Hand2Args::far_epilogue): 1 = the all-far tile program computes the element-wise epilogues of the SDF
+    // network's layers once per row of lanes; 0 = per lane, as the general program does (the same bits)
+    int far_epilogue = 1;
 };
 
 // unset or empty -> 1; first character '0' -> 0; '2' -> 2 where the switch has a third form; anything else -> 1
@@ -33,13 +36,14 @@ inline int env_switch(const char* e, bool has_two) {
     return e[0] == '0' ? 0 : ((has_two && e[0] == '2') ? 2 : 1);
 }
 
-// The three environment switches, read ONCE per C-ABI call, where that call builds its options (a setenv between two calls takes
+// The four environment switches, read ONCE per C-ABI call, where that call builds its options (a setenv between two calls takes
 // effect).  live_first (optional): HONERF_LIVE_FIRST, the single-field render's own switch: 0 = off; 1 = on for launches the field
 // kernel treats as long; 2 = on at every size.
 inline FieldLaunchOpts resolve_launch_opts(int* live_first = nullptr) {
     FieldLaunchOpts o;
     o.uniform_stash = env_switch(getenv("HONERF_UNIFORM_STASH"), true);
     o.far_tiles = env_switch(getenv("HONERF_FAR_TILES"), false);
+    o.far_epilogue = env_switch(getenv("HONERF_FAR_EPILOGUE"), false);
     if (live_first != nullptr) *live_first = env_switch(getenv("HONERF_LIVE_FIRST"), true);
     return o;
 }

@@ -776,7 +776,8 @@ __device__ __forceinline__ void split_finish(EpiState& st) {
 // matters.  kind: 0 softplus(beta=100), 1 g * sigma'(z) from the stashed activation, 2 relu, 3 identity;
 // adjoint (hn_field2_*_adj): 4 forward-direction sweep  v = z sigma',  w = z (1 - sigma') * (pd.x 100 / 256)  (pd.x = dz:
 // w is the second-order source sigma'' u dzb of oracle/field_bwd.py written without a division by sigma');
-// 5 second reverse sweep  v = z sigma' + pd.x;  6 relu mask  v = pd.v > 0 ? z : 0.
+// 5 second reverse sweep  v = z sigma' + pd.x;  6 relu mask  v = pd.v > 0 ? z : 0;  7 (measurement builds, WRONG results) no
+// element-wise work at all: v = c1 and the fragments are conversions of the raw accumulators.
 #ifndef HN_DBG_SOFTPLUS_AS_RELU
 #define HN_DBG_SOFTPLUS_AS_RELU 0   // 1 (measurement only, WRONG results): the softplus epilogue issues a ReLU's instructions -- an upper bound on
                                     // what a cheaper activation epilogue could buy the evaluation kernels (round 5, profiles/r05/README.md)
@@ -785,7 +786,8 @@ template <int J, int P, int KIND_, bool FRAGS, typename PD>
 __device__ __forceinline__ void pair_phase(EpiState& st, const PD& pd) {
     constexpr int KIND = (HN_DBG_SOFTPLUS_AS_RELU && KIND_ == 0) ? 2 : KIND_;
     constexpr int i0 = 2 * J, i1 = 2 * J + 1;
-    if constexpr (P == 0) {
+    if constexpr (P == 0 && KIND == 7) {
+    } else if constexpr (P == 0) {
         const f32x2 c1 = {st.c1[i0], st.c1[i1]}, c2 = {st.c2[i0], st.c2[i1]};
         const f32x2 inv = {st.inv, st.inv};
         st.z2 = c2 * inv + c1;
@@ -816,8 +818,22 @@ __device__ __forceinline__ void pair_phase(EpiState& st, const PD& pd) {
         }
         if constexpr (KIND == 5) v = st.z2 - st.e2 + f32x2{pd.x[i0], pd.x[i1]};
         if constexpr (KIND == 6) v = f32x2{pd.v[i0] > 0.f ? st.z2[0] : 0.f, pd.v[i1] > 0.f ? st.z2[1] : 0.f};
+        if constexpr (KIND == 7) v = f32x2{st.c1[i0], st.c1[i1]};
         st.v[i0] = v[0];
         st.v[i1] = v[1];
+    } else if constexpr (KIND == 7) {
+        // (measurement only, PhRaw below: the two fragments straight from the two accumulators, one conversion per pair each)
+        if constexpr (FRAGS) {
+            constexpr int u = frag_u(i0), j = frag_j(i0);
+            unsigned p2;
+            if constexpr (P == 4) {
+                asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(p2) : "v"(st.c1[i0]), "v"(st.c1[i1]));
+                set_pair<j / 2>(st.hi[u], p2);
+            } else {
+                asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(p2) : "v"(st.c2[i0]), "v"(st.c2[i1]));
+                set_pair<j / 2>(st.lo[u], p2);
+            }
+        }
     } else if constexpr (P == 4) {
         if constexpr (FRAGS) {
             constexpr int u = frag_u(i0), j = frag_j(i0);
@@ -858,6 +874,16 @@ template <typename T>
 struct ph_delay<T, std::void_t<decltype(T::delay)>> {
     static constexpr int value = T::delay;
 };
+// A phase type with `static constexpr bool own_calls = true` runs the 48 calls of a tile epilogue itself (`ph.call<C, FRAGS>(st, pd)`)
+// instead of pair_phase: the shared epilogue of the hand field's all-far tiles (PhFarShared, hn_field2_hand.hip).
+template <typename T, typename = void>
+struct ph_own_calls {
+    static constexpr bool value = false;
+};
+template <typename T>
+struct ph_own_calls<T, std::void_t<decltype(T::own_calls)>> {
+    static constexpr bool value = T::own_calls;
+};
 template <bool FRAGS, typename Ph, typename PD>
 struct Epi {
     static constexpr bool branchy = Ph::branchy;
@@ -867,7 +893,10 @@ struct Epi {
     template <int C>
     __device__ __forceinline__ void call() {
 #if HN_EPI_PAIRS
-        pair_phase<C / 6, C % 6, Ph::kind, FRAGS>(st, pd);
+        if constexpr (ph_own_calls<Ph>::value)
+            ph.template call<C, FRAGS>(st, pd);
+        else
+            pair_phase<C / 6, C % 6, Ph::kind, FRAGS>(st, pd);
 #else
         constexpr int I = C / 3, P = C % 3;
         if constexpr (P < 2)
@@ -1058,6 +1087,11 @@ struct PhRelu {
         constexpr int I = I_::value, P = P_::value;
         if constexpr (P == 0) st.v[I] = fmaxf(fmaf(st.c2[I], st.inv, st.c1[I]), 0.f);
     }
+};
+// measurement builds only (-DHN_DBG_FAR_NO_EPILOGUE=1 of the hand field, WRONG results): pair_phase kind 7
+struct PhRaw {
+    static constexpr int kind = 7;
+    static constexpr bool branchy = HN_BRANCHY_FWD;
 };
 struct PhIdentity {
     static constexpr int kind = 3;

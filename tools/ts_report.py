@@ -15,6 +15,8 @@ n = int(os.environ.get('N_SAMPLES', str(32768 * int(os.environ.get('TILES', '1')
 bt_inv, T_pose, joints = synth.synth_hand_pose(5)
 j = torch.from_numpy(joints)
 p = j[torch.randint(0, 21, (n,), generator=gen)] + 0.03 * torch.randn(n, 3, generator=gen)
+if os.environ.get('FAR'):   # FAR=1: every sample a metre from the hand -- all tiles take the all-far tile program
+    p = j.mean(0) + torch.tensor([0.0, 0.0, 1.25]) + 0.05 * torch.rand(n, 3, generator=gen)
 d = torch.nn.functional.normalize(torch.randn(max(n // 64, 1), 3, generator=gen), dim=-1)
 pc, dc = p.cuda(), d.cuda()
 bt, tp = torch.from_numpy(bt_inv).cuda().reshape(1, 21, 4, 4), torch.from_numpy(T_pose).cuda().reshape(1, 21, 3)
