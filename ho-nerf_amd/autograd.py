@@ -574,3 +574,116 @@ class FitWindowLossFn(torch.autograd.Function):
             gR_o, gt_o, g_bt = gRt, gtt, (gb.reshape(s_b) if s_b is not None else None)
         return (gc.reshape(s_c), gw.reshape(s_w), gsh.reshape(s_h), gso.reshape(s_o), gj_o.reshape(s_j), gR_o.reshape(s_r), gt_o.reshape(s_t),
                 gst.reshape(()) if (ctx.has_stable and term is None) else None, None, None, None, None, None, None, None, g_bt, None)
+
+
+def _f32_scalar(v):
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+class GBuffer2Fn(torch.autograd.Function):
+    """The geometry buffers of a field pair as a differentiable function of the per-sample sdf / gradients a render hands back
+    and of the ray directions (hn_gbuffer2 with Ro = NULL / hn_gbuffer2_bwd):
+    (sdf_h [N*S], grad_h [N*S,3], d_h [N,3], sdf_o, grad_o, d_o, z [N,S]) -> opacity [N,2], depth [N,2], normal [N,2,3], hand then
+    obj, the object's normal in the OBJECT's frame.  The depths carry no gradient.  A buffer the caller's scalar does not use
+    arrives as None in backward and goes to the kernel as NULL."""
+
+    @staticmethod
+    def forward(ctx, sdf_h, grad_h, d_h, sdf_o, grad_o, d_o, z, inv_s_h, inv_s_o, n_frames, sample_dist):
+        L = _lib
+        lib = L.load()
+        z = L.f32(z.detach())
+        S = z.shape[-1]
+        N = z.numel() // S
+        if n_frames < 1 or N % n_frames:
+            raise ValueError('gbuffer2: %d rays are not %d frames of equally many' % (N, n_frames))
+        dev = z.device
+        n = N * S
+        t = [L.f32(x.detach(), dev).reshape(shape) for x, shape in ((sdf_h, (n,)), (grad_h, (n, 3)), (d_h, (N, 3)), (sdf_o, (n,)),
+                                                                    (grad_o, (n, 3)), (d_o, (N, 3)))]
+        z = z.reshape(N, S)
+        ctx.consts = (_f32_scalar(inv_s_h), _f32_scalar(inv_s_o), int(n_frames), N // int(n_frames), S, _f32_scalar(sample_dist))
+        opacity, depth, normal = _empty(N, 2, dev=dev), _empty(N, 2, dev=dev), _empty(N, 2, 3, dev=dev)
+        c = ctx.consts
+        L.check(lib.hn_gbuffer2(L.ptr(t[0]), L.ptr(t[1]), L.ptr(t[2]), c[0], L.ptr(t[3]), L.ptr(t[4]), L.ptr(t[5]), c[1], L.ptr(z), c[2], c[3],
+                                S, c[5], None, L.ptr(opacity), L.ptr(depth), L.ptr(normal), L.stream_ptr()), 'hn_gbuffer2')
+        ctx.save_for_backward(*t, z)
+        ctx.shapes = tuple(x.shape for x in (sdf_h, grad_h, d_h, sdf_o, grad_o, d_o))
+        ctx.set_materialize_grads(False)
+        return opacity, depth, normal
+
+    @staticmethod
+    def backward(ctx, g_opacity, g_depth, g_normal):
+        if g_opacity is None and g_depth is None and g_normal is None:
+            return (None,) * 11
+        L = _lib
+        lib = L.load()
+        sdf_h, grad_h, d_h, sdf_o, grad_o, d_o, z = ctx.saved_tensors
+        N, S = z.shape
+        n, dev = N * S, z.device
+        c = ctx.consts
+        up = [None if g is None else L.f32(g, dev).reshape(shape) for g, shape in ((g_opacity, (N, 2)), (g_depth, (N, 2)), (g_normal, (N, 2, 3)))]
+        gs_h, gg_h, gs_o, gg_o = _empty(n, dev=dev), _empty(n, 3, dev=dev), _empty(n, dev=dev), _empty(n, 3, dev=dev)
+        gd_h = _empty(N, 3, dev=dev) if ctx.needs_input_grad[2] else None
+        gd_o = _empty(N, 3, dev=dev) if ctx.needs_input_grad[5] else None
+        L.check(lib.hn_gbuffer2_bwd(L.ptr(sdf_h), L.ptr(grad_h), L.ptr(d_h), c[0], L.ptr(sdf_o), L.ptr(grad_o), L.ptr(d_o), c[1], L.ptr(z), c[2],
+                                    c[3], S, c[5], L.ptr(up[0]), L.ptr(up[1]), L.ptr(up[2]), L.ptr(gs_h), L.ptr(gg_h), L.ptr(gs_o), L.ptr(gg_o),
+                                    L.ptr(gd_h), L.ptr(gd_o), L.stream_ptr()), 'hn_gbuffer2_bwd')
+        s = ctx.shapes
+        need = ctx.needs_input_grad
+        outs = (gs_h, gg_h, gd_h, gs_o, gg_o, gd_o)
+        return tuple(o.reshape(s[i]) if (need[i] and o is not None) else None for i, o in enumerate(outs)) + (None,) * 5
+
+
+class GBuffer1Fn(torch.autograd.Function):
+    """The geometry buffers of one field (hn_gbuffer1 / hn_gbuffer1_bwd): (sdf [N*S], grad [N*S,3], d [N,3], z [N,S]) -> opacity [N],
+    depth [N], normal [N,3] in the field's frame; the transmittance is seeded with c_0 as in the single-field render."""
+
+    @staticmethod
+    def forward(ctx, sdf, grad, d, z, inv_s, sample_dist):
+        L = _lib
+        lib = L.load()
+        z = L.f32(z.detach())
+        S = z.shape[-1]
+        N = z.numel() // S
+        dev = z.device
+        n = N * S
+        t = [L.f32(x.detach(), dev).reshape(shape) for x, shape in ((sdf, (n,)), (grad, (n, 3)), (d, (N, 3)))]
+        z = z.reshape(N, S)
+        ctx.consts = (_f32_scalar(inv_s), _f32_scalar(sample_dist))
+        opacity, depth, normal = _empty(N, dev=dev), _empty(N, dev=dev), _empty(N, 3, dev=dev)
+        L.check(lib.hn_gbuffer1(L.ptr(t[0]), L.ptr(t[1]), L.ptr(t[2]), L.ptr(z), N, S, ctx.consts[1], ctx.consts[0], L.ptr(opacity),
+                                L.ptr(depth), L.ptr(normal), L.stream_ptr()), 'hn_gbuffer1')
+        ctx.save_for_backward(*t, z)
+        ctx.shapes = tuple(x.shape for x in (sdf, grad, d))
+        ctx.set_materialize_grads(False)
+        return opacity, depth, normal
+
+    @staticmethod
+    def backward(ctx, g_opacity, g_depth, g_normal):
+        if g_opacity is None and g_depth is None and g_normal is None:
+            return (None,) * 6
+        L = _lib
+        lib = L.load()
+        sdf, grad, d, z = ctx.saved_tensors
+        N, S = z.shape
+        n, dev = N * S, z.device
+        up = [None if g is None else L.f32(g, dev).reshape(shape) for g, shape in ((g_opacity, (N,)), (g_depth, (N,)), (g_normal, (N, 3)))]
+        gs, gg = _empty(n, dev=dev), _empty(n, 3, dev=dev)
+        gd = _empty(N, 3, dev=dev) if ctx.needs_input_grad[2] else None
+        L.check(lib.hn_gbuffer1_bwd(L.ptr(sdf), L.ptr(grad), L.ptr(d), L.ptr(z), N, S, ctx.consts[1], ctx.consts[0], L.ptr(up[0]), L.ptr(up[1]),
+                                    L.ptr(up[2]), L.ptr(gs), L.ptr(gg), L.ptr(gd), L.stream_ptr()), 'hn_gbuffer1_bwd')
+        s = ctx.shapes
+        need = ctx.needs_input_grad
+        outs = (gs, gg, gd)
+        return tuple(o.reshape(s[i]) if (need[i] and o is not None) else None for i, o in enumerate(outs)) + (None,) * 3
+
+
+def gbuffer2(sdf_h, grad_h, d_h, inv_s_h, sdf_o, grad_o, d_o, inv_s_o, z, n_frames, sample_dist):
+    """opacity [N,2], depth [N,2], normal [N,2,3] (hand, obj; the object's normal in its own frame) of a field pair, differentiable
+    w.r.t. the sdf, the gradients and the ray directions of both fields; `z` [N,S] carries no gradient."""
+    return GBuffer2Fn.apply(sdf_h, grad_h, d_h, sdf_o, grad_o, d_o, z, inv_s_h, inv_s_o, n_frames, sample_dist)
+
+
+def gbuffer1(sdf, grad, d, inv_s, z, sample_dist):
+    """opacity [N], depth [N], normal [N,3] of one field, differentiable w.r.t. sdf, grad and d; `z` [N,S] carries no gradient."""
+    return GBuffer1Fn.apply(sdf, grad, d, z, inv_s, sample_dist)

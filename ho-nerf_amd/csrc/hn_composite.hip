@@ -193,11 +193,6 @@ __device__ __forceinline__ float row_max(float v) {
     v = fmaxf(v, dpp<0x121>(0.f, v));
     return v;
 }
-template <int CPS>
-__device__ __forceinline__ void store_run(float* __restrict__ p, const float (&v)[CPS]) {
-#pragma unroll
-    for (int q = 0; q < CPS / 4; ++q) reinterpret_cast<float4*>(p)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-}
 __device__ __forceinline__ float wave_sum_rows(float v) {   // v is already a row sum (equal within a row)
     v += __shfl_xor(v, 16, 64);
     v += __shfl_xor(v, 32, 64);
@@ -367,14 +362,9 @@ __global__ void k_alpha_bwd(const float* __restrict__ sdf, const float* __restri
     const float A = (c - nx) + 1e-5f, B = c + 1e-5f;
     const float a_raw = A / B;
     const float ga = (a_raw > 0.f && a_raw < 1.f) ? g_alpha[i] : 0.f;   // clip(0, 1)
-    // a = A / B: da/dc = (B - A) / B^2, da/dnx = -1 / B
-    float gc = ga * (B - A) / (B * B) + (g_c != nullptr ? g_c[i] : 0.f);
-    float gnx = -ga / B;
-    const float gx1 = gc * inv_s * c * (1.f - c);      // x1 = s - half
-    const float gx2 = gnx * inv_s * nx * (1.f - nx);   // x2 = s + half
-    g_sdf[i] = gx1 + gx2;
-    const float ghalf = gx2 - gx1;
-    const float gtc = (tc < 0.f) ? ghalf * dist * 0.5f : 0.f;   // ic = min(tc, 0)
+    float gs, gtc;
+    alpha_sample_bwd<true>(c, nx, tc, dist, inv_s, ga, g_c != nullptr ? g_c[i] : 0.f, gs, gtc);
+    g_sdf[i] = gs;
     g_grad[3 * (size_t)i] = gtc * d0;
     g_grad[3 * (size_t)i + 1] = gtc * d1;
     g_grad[3 * (size_t)i + 2] = gtc * d2;
@@ -774,13 +764,8 @@ __global__ __launch_bounds__(256) void k_alpha_bwd_up(const float* __restrict__ 
     const float A = (c - nx) + 1e-5f, B = c + 1e-5f;
     const float a_raw = A / B;
     const float ga = (a_raw > 0.f && a_raw < 1.f) ? g_alpha[i] : 0.f;   // clip(0, 1)
-    const float gc = ga * (B - A) / (B * B);
-    const float gnx = -ga / B;
-    const float gx1 = gc * inv_s * c * (1.f - c);
-    const float gx2 = gnx * inv_s * nx * (1.f - nx);
-    float o_s = gx1 + gx2;
-    const float ghalf = gx2 - gx1;
-    const float gtc = (tc < 0.f) ? ghalf * dist * 0.5f : 0.f;
+    float o_s, gtc;
+    alpha_sample_bwd<false>(c, nx, tc, dist, inv_s, ga, 0.f, o_s, gtc);
     float o_g[3] = {gtc * d0, gtc * d1, gtc * d2};
     // (the same association as the two launches this replaces: (alpha part) + direct, then + eikonal)
     if (g_sdf_out != nullptr) o_s += g_sdf_out[i];

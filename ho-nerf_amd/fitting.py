@@ -95,6 +95,41 @@ def render_loss_terms(render_out, true_rgb, true_mask, fit_type='1', video=False
     return terms
 
 
+def geometry_loss_terms(buffers, true_depth=None, true_label=None):
+    """Loss terms on the geometry buffers of `render_buffers(graph=True)` against what an RGB-D capture with a hand / object
+    segmentation measures per ray; the reference has neither.  true_depth [P] in metres along the ray (0 = no
+    measurement), true_label [P] (0 background, 1 hand, 2 object); [F,P] with the frame-batched renderer.  Returns the scalars
+      depth                 over the rays with true_depth > 0, the mean of |depth_hand + depth_obj - (opacity_hand + opacity_obj) true_depth|:
+                            the expected depth against the measured one, multiplied through by the opacity instead of divided by it
+      mask_hand, mask_obj   BCE(clip(opacity_f, 1e-3, 1 - 1e-3), true_label == 1 / == 2): the clip and form of the merged-mask term
+    A few torch operators on [P] tensors; a target that is None leaves its terms out."""
+    terms = {}
+    oh, oo = buffers['opacity_hand'].reshape(-1), buffers['opacity_obj'].reshape(-1)
+    if true_depth is not None:
+        td = true_depth.reshape(-1).to(oh.dtype)
+        valid = (td > 0).to(oh.dtype)
+        resid = (buffers['depth_hand'].reshape(-1) + buffers['depth_obj'].reshape(-1) - (oh + oo) * td).abs()
+        terms['depth'] = (resid * valid).sum() / valid.sum().clamp_min(1.0)
+    if true_label is not None:
+        lab = true_label.reshape(-1)
+        terms['mask_hand'] = F.binary_cross_entropy(oh.clip(1e-3, 1.0 - 1e-3), (lab == 1).to(oh.dtype))
+        terms['mask_obj'] = F.binary_cross_entropy(oo.clip(1e-3, 1.0 - 1e-3), (lab == 2).to(oh.dtype))
+    return terms
+
+
+def _geometry_weights(geometry):
+    bad = set(geometry) - {'depth_weight', 'mask_weight'}
+    if bad:
+        raise ValueError('geometry: unknown keys %s (depth_weight, mask_weight)' % sorted(bad))
+    return float(geometry.get('depth_weight', 0.0)), float(geometry.get('mask_weight', 0.0))
+
+
+def _refuse_geometry(geometry, who):
+    if geometry is not None:
+        raise ValueError('%s builds no autograd graph through the render, so it cannot take the geometry terms: use fit_step(..., geometry=...)'
+                         % who)
+
+
 class FrameShardedRunner:
     """Runs `frame_fn(frame_id) -> dict of scalar tensors/floats` over this rank's frames and
     reduces the sums over all ranks.
@@ -477,10 +512,13 @@ def bone_lengths_of(joints_mano):
 
 
 # ---- one optimisation step --------------------------------------------------------------------------------------------
-def step_loss(render_out, true_rgb, true_mask, pose, fit_type='1', video=False, smooth_ends=(False, False), stable=None, pose_terms=None):
+def step_loss(render_out, true_rgb, true_mask, pose, fit_type='1', video=False, smooth_ends=(False, False), stable=None, pose_terms=None,
+              geometry=None):
     """The full loss of one step: fitting_single.py:251-283 (video=False) or fitting_video.py:285-334 (video=True:
     + smoothness over the window's frames x50, anchored to the prediction at the sequence ends; + 100 x the stable
-    term for fit type '1234').  `pose` is the pose chain's output dict."""
+    term for fit type '1234').  `pose` is the pose chain's output dict.  The geometry terms are not this function's: its fused forms
+    are single launches with no input for them, and fit_step / fit_backward add them to this sum."""
+    _refuse_geometry(geometry, 'step_loss (the fused step / window loss)')
     if not video and render_out['color_fine'].is_cuda and 'obj_verts' in pose and pose['joint_3d'].shape[0] == 1:
         # fitting_single on the device: the whole loss is one autograd node over five launches (autograd.FitStepLossFn)
         from .autograd import FitStepLossFn
@@ -600,7 +638,7 @@ def _unit_gradient(loss):
 
 
 def fit_backward(renderer, view, pose_chain, near, far, fit_type='1', index=None, smooth_ends=(False, False),
-                 obj_verts_for_stable=None, t_rand=None, rays_fn=None):
+                 obj_verts_for_stable=None, t_rand=None, rays_fn=None, geometry=None):
     """The forward + backward half of one optimiser step of the fitting loops: pose chain -> rays of the view's sampled
     pixels (`_xy_to_ray_bundle` -> hn_ray_gen) -> renderer.render -> losses -> backward into the pose parameters
     (fitting_single.py:201-290; batched renderer: fitting_video.py:212-341).  The parameters' `.grad` are cleared first
@@ -608,8 +646,16 @@ def fit_backward(renderer, view, pose_chain, near, far, fit_type='1', index=None
 
     view: dict(cam={'R','T','focal','principal'} device tensors [n_cams,..], xy [n_cams*P,2] NDC, true_rgb, true_mask)
     with n_cams = 1 for fitting_single and the window's 4 cameras for fitting_video.  `rays_fn(xy, cam, n_cams, P)`
-    replaces hn_ray_gen (host-logic tests over a stub renderer; the product path never passes it)."""
+    replaces hn_ray_gen (host-logic tests over a stub renderer; the product path never passes it).
+
+    geometry: dict(depth_weight=.., mask_weight=..) -- when the view also carries `true_depth` / `true_label` (geometry_loss_terms), the
+    step renders through `render_buffers(graph=True)` and adds depth_weight * depth + mask_weight * (mask_hand + mask_obj) to the loss;
+    the unweighted terms come back under those names.  None (the default): the launches of a step are what they were."""
     video = bool(getattr(renderer, 'batched', False))
+    geo = geometry is not None and (view.get('true_depth') is not None or view.get('true_label') is not None)
+    if geo:
+        depth_w, mask_w = _geometry_weights(geometry)
+    render = (lambda *a, **k: renderer.render_buffers(*a, graph=True, **k)) if geo else renderer.render
     for p in pose_chain.parameters():
         p.grad = None
     # A window step with the stable term: the chain's Jacobian goes to the extra stream BEHIND the stable term's forward pass (its
@@ -677,14 +723,14 @@ def fit_backward(renderer, view, pose_chain, near, far, fit_type='1', index=None
             Ro_arg = Mat3InverseFn.apply(pose['obj_r'])                                # fitting_video.py:284, one launch each way
         else:
             Ro_arg = torch.inverse(pose['obj_r'])                                      # fitting_video.py:284
-        out = renderer.render(rays_o.reshape(n_cams, P, 3), rays_d.reshape(n_cams, P, 3), near, far, pose['bt_inv'], T_pose, None,
-                              Ro_arg, pose['obj_t'], t_rand=t_rand)
+        out = render(rays_o.reshape(n_cams, P, 3), rays_d.reshape(n_cams, P, 3), near, far, pose['bt_inv'], T_pose, None,
+                     Ro_arg, pose['obj_t'], t_rand=t_rand)
     else:
         # frame 0 of a one-frame chain as a reshape: the backward of `x[0]` is a zero fill and a copy per tensor, that of a view is free
         one = pose['bt_inv'].shape[0] == 1
         first = lambda x: x.reshape(x.shape[1:]) if one else x[0]
         Ro_arg = first(pose['obj_r']).T                                                # fitting_single.py:250
-        out = renderer.render(rays_o, rays_d, near, far, first(pose['bt_inv']), first(T_pose), None, Ro_arg, first(pose['obj_t']), t_rand=t_rand)
+        out = render(rays_o, rays_d, near, far, first(pose['bt_inv']), first(T_pose), None, Ro_arg, first(pose['obj_t']), t_rand=t_rand)
     if side is not None:
         main = torch.cuda.current_stream()
         main.wait_stream(side)
@@ -692,6 +738,11 @@ def fit_backward(renderer, view, pose_chain, near, far, fit_type='1', index=None
         for x in shared + (list(pterms.values()) if pterms is not None else []):
             x.record_stream(main)
     terms = step_loss(out, view['true_rgb'], view['true_mask'], pose, fit_type, video, smooth_ends, stable, pterms)
+    if geo:
+        gt = geometry_loss_terms(out, view.get('true_depth'), view.get('true_label'))
+        extra = sum(w * gt[k] for k, w in (('depth', depth_w), ('mask_hand', mask_w), ('mask_obj', mask_w)) if k in gt)
+        terms = dict(terms, **gt)
+        terms['loss'] = terms['loss'] + extra
     terms['loss'].backward(gradient=_unit_gradient(terms['loss']))
     return terms
 
@@ -709,15 +760,15 @@ def fit_apply(optimizer, pose_chain=None, dist=None, sync=False):
 
 
 def fit_step(renderer, view, pose_chain, optimizer, near, far, fit_type='1', index=None, smooth_ends=(False, False),
-             obj_verts_for_stable=None, t_rand=None, rays_fn=None, pipelined=False):
+             obj_verts_for_stable=None, t_rand=None, rays_fn=None, pipelined=False, geometry=None):
     """One optimiser step of the fitting loops on one rank: `fit_backward` then `fit_apply` without a collective
     (fitting_single.py:201-291; fitting_video.py:212-342).  pipelined: where it applies (fitting_single on the device, the
     reference's pose chain, PoseAdam) the step runs as PipelinedSingleFit -- same kernels, the hand's and the object's halves on two
     streams that stay apart across steps; call `finish_pipeline(optimizer)` (or synchronise the device) before reading the
     parameters.  `fit_frame` does both."""
-    if pipelined and PipelinedSingleFit.applicable(renderer, pose_chain, optimizer, fit_type, index, rays_fn):
+    if geometry is None and pipelined and PipelinedSingleFit.applicable(renderer, pose_chain, optimizer, fit_type, index, rays_fn):
         return pipelined_fit(renderer, pose_chain, optimizer, near, far, fit_type).step(view, t_rand)
-    terms = fit_backward(renderer, view, pose_chain, near, far, fit_type, index, smooth_ends, obj_verts_for_stable, t_rand, rays_fn)
+    terms = fit_backward(renderer, view, pose_chain, near, far, fit_type, index, smooth_ends, obj_verts_for_stable, t_rand, rays_fn, geometry)
     fit_apply(optimizer)
     return terms
 
@@ -884,9 +935,10 @@ class PipelinedSingleFit:
                 and pose_chain.joints0.is_cuda and pose_chain.joints0.shape[0] == frames and 1 <= frames <= PipelinedSingleFit.MAX_FRAMES
                 and (renderer.precision or 'f16x3') == 'f16x3' and renderer.n_importance > 0)
 
-    def __init__(self, renderer, pose_chain, optimizer, near, far, fit_type):
+    def __init__(self, renderer, pose_chain, optimizer, near, far, fit_type, geometry=None):
         import ctypes
         from . import lib as L
+        _refuse_geometry(geometry, 'PipelinedSingleFit')
         self.L, self.lib = L, L.load()
         self.ren, self.chain, self.opt = renderer, pose_chain, optimizer
         self.near, self.far, self.fit_type = float(near), float(far), fit_type
@@ -1002,10 +1054,12 @@ class PipelinedSingleFit:
         return parts[0] if self.F == 1 else torch.cat(parts, dim=1)
 
     @torch.no_grad()
-    def step(self, view, t_rand=None):
+    def step(self, view, t_rand=None, geometry=None):
         """-> the step's loss terms (device scalars, as fit_step returns them; [F] vectors for a chain of F > 1 frames).  The six
         leaves' .grad hold the step's gradient.  view: the step's pixels -- for F frames `cam` holds F cameras and xy / true_rgb /
-        true_mask the F frames' R rows each, frame after frame (`stack_views`)."""
+        true_mask the F frames' R rows each, frame after frame (`stack_views`).  The step is explicit launches each way, no
+        autograd graph: the geometry terms (fit_step's `geometry`) are refused."""
+        _refuse_geometry(geometry, 'PipelinedSingleFit.step')
         L, lib, ren, ch = self.L, self.lib, self.ren, self.chain
         dev = self.dev
         Fr = self.F
@@ -1161,10 +1215,11 @@ def finish_pipeline(optimizer):
         cur[1].finish()
 
 
-def fit_frame(renderer, views, pose_chain, near, far, fit_type='1', n_iters=None, sample_view=None, rays_fn=None):
+def fit_frame(renderer, views, pose_chain, near, far, fit_type='1', n_iters=None, sample_view=None, rays_fn=None, geometry=None):
     """fitting_single.py:200-291 for one frame: `n_iters` (30 for fit type '1', 25 for '12'; 40 / 35 with 3 views,
     :124-132) passes over the views, one Adam step per view.  `sample_view(view_id, step) -> view dict` draws the
-    step's pixels (the reference: get_rays_xy on the view's mask, 196 rays); default: the views as given."""
+    step's pixels (the reference: get_rays_xy on the view's mask, 196 rays); default: the views as given.  geometry: fit_step's
+    (the steps then run through autograd, not as PipelinedSingleFit)."""
     if n_iters is None:
         n_iters = {('1', False): 30, ('1', True): 40, ('12', False): 25, ('12', True): 35}[(fit_type, len(views) == 3)]
     opt = make_optimizer(pose_chain, video=False)
@@ -1172,7 +1227,7 @@ def fit_frame(renderer, views, pose_chain, near, far, fit_type='1', n_iters=None
     for _ in range(n_iters):
         for vid in range(len(views)):
             view = sample_view(vid, step) if sample_view is not None else views[vid]
-            last = fit_step(renderer, view, pose_chain, opt, near, far, fit_type, rays_fn=rays_fn, pipelined=PIPELINE_SINGLE)
+            last = fit_step(renderer, view, pose_chain, opt, near, far, fit_type, rays_fn=rays_fn, pipelined=PIPELINE_SINGLE, geometry=geometry)
             step += 1
     finish_pipeline(opt)
     return last, step
@@ -1202,13 +1257,14 @@ def frames_batchable(renderer, frames, fit_type, rays_fn=None):
     return all(len(fr[0]) == len(v0) and all(a['xy'].shape == b['xy'].shape and a['cam']['R'].shape[0] == 1 for a, b in zip(fr[0], v0)) for fr in frames)
 
 
-def fit_frames_batched(renderer, frames, near, far, fit_type='12', n_iters=None, jitter_states=None):
+def fit_frames_batched(renderer, frames, near, far, fit_type='12', n_iters=None, jitter_states=None, geometry=None):
     """fitting_single.py:200-291 for SEVERAL frames at once: `frames` = [(views, chain[, sample_view]), ...], every one its own
     optimisation problem (own six leaves, own Adam moments), all of them stepped through the SAME launches (PipelinedSingleFit over
     the stacked chain): per frame the same kernels on the same numbers as `fit_frame` of that frame alone, to the bit -- the batch is
     a way to fill the GPU when a rank owns more than one frame, not a change of the fit.  jitter_states: per frame the state of the
     CUDA generator its jitter is to be drawn from (what the global generator held when the frame's data was made: `fit_frame` draws
     from there), None: the global generator for all.  -> ([terms of the last step per frame], steps per frame)."""
+    _refuse_geometry(geometry, 'fit_frames_batched')
     Fr = len(frames)
     chains = [fr[1] for fr in frames]
     n_views = len(frames[0][0])
@@ -1236,7 +1292,7 @@ def fit_frames_batched(renderer, frames, near, far, fit_type='12', n_iters=None,
 
 
 def fit_window(renderer, views, pose_chain, optimizer, near, far, index, data_num, fit_type='1234', first_pass=False,
-               obj_verts=None, sample_view=None, sub_iters=4, rays_fn=None, n_views=None):
+               obj_verts=None, sample_view=None, sub_iters=4, rays_fn=None, n_views=None, geometry=None):
     """fitting_video.py:211-342 for one window of 4 consecutive frames `index`: 4 sub-iterations x the views, an
     Adam step each on the shared [data_num, ..] parameters.  The smoothness term is anchored to the prediction when
     the window touches either end of the sequence (not on the very first step, :312)."""
@@ -1247,7 +1303,7 @@ def fit_window(renderer, views, pose_chain, optimizer, near, far, index, data_nu
             later = not (first_pass and sub == 0 and vid == 0)
             ends = (later and int(index[0]) == 0, later and int(index[-1]) == data_num - 1)
             last = fit_step(renderer, view, pose_chain, optimizer, near, far, fit_type, index=index, smooth_ends=ends,
-                            obj_verts_for_stable=obj_verts, rays_fn=rays_fn)
+                            obj_verts_for_stable=obj_verts, rays_fn=rays_fn, geometry=geometry)
             step += 1
     return last, step
 
@@ -1412,11 +1468,17 @@ def pose_saver(directory, fit_type, gt=None, name=str):
     return _PoseSaver(directory, fit_type, gt, name)
 
 
-def synthetic_views(n_views, n_frames, rays_per_frame, seed, joints_center, device='cuda', H=230, W=266):
+def synthetic_views(n_views, n_frames, rays_per_frame, seed, joints_center, device='cuda', H=230, W=266, with_geometry=None):
     """Synthetic stand-in for one fit_*_dataset item (the data set is an external download): `n_views` ring cameras
     looking at the hand, per view `rays_per_frame` pixels per frame drawn from a synthetic mask (NDC convention of
     utils/dataset.py:45-47), random target colours, mask = 1 inside.  n_frames > 1 lays the window's frames out as
-    [F*P] rows with one camera per frame (all frames of a window share the view's camera, fitting_video.py:213-222)."""
+    [F*P] rows with one camera per frame (all frames of a window share the view's camera, fitting_video.py:213-222).
+
+    with_geometry: dict(renderer=, near=, far=, bt_inv=, T_pose_21=, Ro=, To=[, opacity_threshold=0.5]) -- the ground-truth pose as
+    `renderer.render` takes it ([F,..] for the frame-batched class).  Every view then also carries what a depth camera and a
+    segmentation would give on its pixels, by harness.render_view_buffers' rules on `render_buffers` at that pose: `true_label`
+    (0 where opacity_hand + opacity_obj is under the threshold, else 1 hand / 2 object by the larger opacity) and `true_depth`
+    (depth / opacity in metres along the ray where something is seen, 0 elsewhere), both [P] ([F,P] for n_frames > 1)."""
     from . import synth
     cams = synth.ring_cameras(n_views, radius=0.9, target=tuple(joints_center), focal=2.0, seed=seed)
     g = torch.Generator('cpu').manual_seed(seed)
@@ -1429,4 +1491,22 @@ def synthetic_views(n_views, n_frames, rays_per_frame, seed, joints_center, devi
         views.append({'cam': cam, 'xy': torch.from_numpy(xy).to(device).contiguous(),
                       'true_rgb': torch.rand(*shape, 3, generator=g).to(device),
                       'true_mask': (torch.rand(*shape, 1, generator=g) > 0.2).float().to(device)})
+        if with_geometry is not None:
+            views[-1].update(_geometry_targets(views[-1], n_frames, rays_per_frame, **with_geometry))
     return views
+
+
+def _geometry_targets(view, n_frames, rays_per_frame, renderer, near, far, bt_inv, T_pose_21, Ro, To, opacity_threshold=0.5):
+    from . import lib as L
+    rays_o, rays_d = _rays(L, view['xy'], view['cam'], n_frames, rays_per_frame)
+    if getattr(renderer, 'batched', False):
+        rays_o, rays_d = rays_o.reshape(n_frames, rays_per_frame, 3), rays_d.reshape(n_frames, rays_per_frame, 3)
+    with torch.no_grad():
+        b = renderer.render_buffers(rays_o, rays_d, near, far, bt_inv, T_pose_21, None, Ro, To)
+    oh, oo = b['opacity_hand'][..., 0], b['opacity_obj'][..., 0]
+    op = oh + oo
+    seen = op >= float(opacity_threshold)
+    label = torch.where(seen, torch.where(oh >= oo, 1, 2), 0).to(torch.uint8)
+    depth = torch.where(seen, b['depth'][..., 0] / op.clamp_min(1e-30), torch.zeros_like(op))
+    shape = (n_frames, rays_per_frame) if n_frames > 1 else (rays_per_frame,)
+    return {'true_depth': depth.reshape(shape), 'true_label': label.reshape(shape)}

@@ -99,6 +99,9 @@ SIGNATURES = {
     'hn_composite2_bwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, c_vp]),
     'hn_gbuffer1': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_fl, c_fl, c_f, c_f, c_f, c_vp]),
     'hn_gbuffer2': (c_i, [c_f, c_f, c_f, c_fl, c_f, c_f, c_f, c_fl, c_f, c_i, c_i, c_i, c_fl, c_f, c_f, c_f, c_f, c_vp]),
+    'hn_gbuffer1_bwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_fl, c_fl, c_f, c_f, c_f, c_f, c_f, c_f, c_vp]),
+    'hn_gbuffer2_bwd': (c_i, [c_f, c_f, c_f, c_fl, c_f, c_f, c_f, c_fl, c_f, c_i, c_i, c_i, c_fl, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f,
+                              c_vp]),
     'hn_fit_loss_sums': (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_vp]),
     'hn_fit_loss_grads': (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_vp]),
     'hn_adam_step': (c_i, [c_i, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_i),

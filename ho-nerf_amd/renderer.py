@@ -478,14 +478,19 @@ class NeuSRenderer_fitting:
             'gradient_obj': o['grad_obj'],
         }
 
-    def render_buffers(self, rays_o, rays_d, near, far, bt_inv, T_pose_21, verts, Ro, To, get_SDF=False, t_rand=None):
+    def render_buffers(self, rays_o, rays_d, near, far, bt_inv, T_pose_21, verts, Ro, To, get_SDF=False, t_rand=None, *, graph=False):
         """`render`'s dictionary plus the geometry the renderer holds per ray, from that render's own per-sample sdf / gradients and
         final depths in one launch (hn_gbuffer2; the object's ray directions through hn_obj_local_fwd first):
           opacity_hand, opacity_obj [B,1]      sum_k w^f_k (their sum is weight_sum)
           depth_hand, depth_obj, depth [B,1]   sum_k w^f_k m_k over the section mid-points, and the sum over the fields: NOT divided by
                                                the opacity (the expected depth of a pixel is depth / (opacity_hand + opacity_obj))
           normal_hand, normal_obj, normal [B,3] sum_k w^f_k grad^f_k in the world frame, and the sum over the fields
-        ([F,P,..] for the frame-batched class).  No tape, no graph: an input that requires grad is refused."""
+        ([F,P,..] for the frame-batched class).  No tape, no graph: an input that requires grad is refused -- unless `graph` is set:
+        then the same keys and shapes come back attached to the autograd graph of the pose-dependent inputs (`render`'s
+        differentiable form, the object's ray directions through ObjLocalFn, autograd.gbuffer2 and the object normal's rotation to
+        the world frame as a torch operator: DESIGN.md 3.25); with nothing that requires grad among the inputs no graph is built."""
+        if graph:
+            return self._render_buffers_graph(rays_o, rays_d, near, far, bt_inv, T_pose_21, verts, Ro, To, get_SDF, t_rand)
         if _wants_grad(rays_o, rays_d, bt_inv, T_pose_21, Ro, To):
             raise ValueError('render_buffers builds no graph: an input requires grad; differentiate through render')
         with torch.no_grad():
@@ -515,6 +520,36 @@ class NeuSRenderer_fitting:
                        depth=depth.sum(-1).reshape(*lead, 1), normal_hand=normal[:, 0].reshape(*lead, 3),
                        normal_obj=normal[:, 1].reshape(*lead, 3), normal=normal.sum(1).reshape(*lead, 3))
             return out
+
+    def _render_buffers_graph(self, rays_o, rays_d, near, far, bt_inv, T_pose_21, verts, Ro, To, get_SDF, t_rand):
+        """render_buffers(graph=True): the buffers as differentiable functions of what `render` is differentiable in."""
+        from .autograd import gbuffer2
+        from .training import ObjLocalFn
+        out = dict(self.render(rays_o, rays_d, near, far, bt_inv, T_pose_21, verts, Ro, To, get_SDF, t_rand=t_rand))
+        hand, obj = self.fields()
+        dev = out['sdf_hand'].device
+        g = lambda x: (x if isinstance(x, torch.Tensor) else torch.as_tensor(x)).to(device=dev, dtype=torch.float32)
+        ro, rd = g(rays_o), g(rays_d)
+        if not self.batched:
+            ro, rd = ro.reshape(1, -1, 3), rd.reshape(1, -1, 3)
+        F, P = ro.shape[0], ro.shape[1]
+        N = F * P
+        z = self._last_z_raw
+        Ro_, To_ = g(Ro).reshape(F, 3, 3), g(To).reshape(F, 3)
+        # the object's directions frame by frame: ObjLocalFn is the one-frame form of hn_obj_local_fwd / _bwd
+        d2 = torch.cat([ObjLocalFn.apply(ro[f], rd[f], Ro_[f], To_[f])[1] for f in range(F)], 0) if F > 1 else \
+            ObjLocalFn.apply(ro[0], rd[0], Ro_[0], To_[0])[1]
+        opacity, depth, normal = gbuffer2(out['sdf_hand'], out['gradient_hand'], rd.reshape(N, 3), float(hand.inv_s), out['sdf_obj'],
+                                          out['gradient_obj'], d2, float(obj.inv_s), z, F, (float(far) - float(near)) / self.n_samples)
+        # the object's normal back to the world frame, Ro^T n (row vectors), as a torch operator: its g_Ro comes from autograd
+        normal_obj = torch.einsum('fpj,fji->fpi', normal[:, 1].reshape(F, P, 3), Ro_).reshape(N, 3)
+        normal_hand = normal[:, 0]
+        lead = (F, P) if self.batched else (N,)
+        out.update(opacity_hand=opacity[:, 0].reshape(*lead, 1), opacity_obj=opacity[:, 1].reshape(*lead, 1),
+                   depth_hand=depth[:, 0].reshape(*lead, 1), depth_obj=depth[:, 1].reshape(*lead, 1),
+                   depth=depth.sum(-1).reshape(*lead, 1), normal_hand=normal_hand.reshape(*lead, 3),
+                   normal_obj=normal_obj.reshape(*lead, 3), normal=(normal_hand + normal_obj).reshape(*lead, 3))
+        return out
 
     def _render_autograd(self, rays_o, rays_d, near, far, bt_inv, T_pose_21, Ro, To, t_rand, lead):
         """The same render with the outputs attached to the autograd graph of the pose-dependent inputs

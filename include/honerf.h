@@ -390,6 +390,21 @@ int hn_gbuffer2(const float* sdf_hand, const float* grad_hand, const float* rays
                 const float* sdf_obj, const float* grad_obj, const float* rays_d_obj, float inv_s_obj,
                 const float* z_vals, int n_frames, int rays_per_frame, int S, float sample_dist, const float* Ro,
                 float* opacity, float* depth, float* normal, hn_stream_t stream);
+/* The adjoint of the two above: per-ray upstream gradients g_opacity, g_depth, g_normal (the outputs' shapes; each may be NULL = zero)
+ * -> per-sample g_sdf [N*S], g_grad [N*S,3] (required) and per-ray g_rays_d [N,3] (each may be NULL = not wanted), overwritten, not
+ * accumulated.  The depths carry no gradient.  The object's g_normal is taken in the OBJECT's frame (what hn_gbuffer2 writes with
+ * Ro = NULL): rotating the normal and its gradient is the caller's.  One launch, no workspace, no allocation, no synchronisation,
+ * no atomics: two calls give the same bits.  S < 1, a negative count, a NULL input or required output, or all three upstream
+ * pointers NULL is HN_EINVAL with a message, before anything is launched; N = 0 launches nothing and returns 0. */
+int hn_gbuffer1_bwd(const float* sdf, const float* grad, const float* rays_d, const float* z_vals, int n_rays, int S, float sample_dist,
+                    float inv_s, const float* g_opacity, const float* g_depth, const float* g_normal, float* g_sdf, float* g_grad,
+                    float* g_rays_d, hn_stream_t stream);
+int hn_gbuffer2_bwd(const float* sdf_hand, const float* grad_hand, const float* rays_d_hand, float inv_s_hand,
+                    const float* sdf_obj, const float* grad_obj, const float* rays_d_obj, float inv_s_obj,
+                    const float* z_vals, int n_frames, int rays_per_frame, int S, float sample_dist,
+                    const float* g_opacity, const float* g_depth, const float* g_normal,
+                    float* g_sdf_hand, float* g_grad_hand, float* g_sdf_obj, float* g_grad_obj,
+                    float* g_rays_d_hand, float* g_rays_d_obj, hn_stream_t stream);
 
 /* ---- whole renders ----------------------------------------------------------------------
  * NeuSRenderer.render (utils/renderer.py:190-258).  rays already in the field's frame
