@@ -45,6 +45,10 @@
                                    // layers of the reverse sweep) issue no phase work: the next layer's fragments are conversions of the raw
                                    // accumulators and a_l is not read back -- an upper bound on what the shared epilogue can buy (profiles/r11)
 #endif
+#ifndef HN_DBG_FAR_STREAM_BARRIERS
+#define HN_DBG_FAR_STREAM_BARRIERS 0   // 1 (measurement only, the same results): the all-far program that fetches no table chunk keeps the full
+                                       // stream's s_waitcnt vmcnt(0) + s_barrier in front of every chunk group all the same
+#endif
 #ifndef HN_DEFER_STASH
 #define HN_DEFER_STASH 0   // 1: the fp32 activation tiles of the hidden layers go to the stash one chunk late (to_regs_hold): measured, no gain
 #endif
@@ -85,6 +89,9 @@ struct Hand2Args {
                      // whose four waves are all far runs the all-far tile program (FarStash below); 0 = every tile runs the general one
     int far_epilogue;   // HONERF_FAR_EPILOGUE (FieldLaunchOpts::far_epilogue): the all-far program computes the SDF layers' element-wise
                         // epilogues once per row of lanes (PhFarShared below); 0 = per lane, as the general program does
+    int far_stream;   // HONERF_FAR_STREAM (FieldLaunchOpts::far_stream): the all-far program with the shared epilogue fetches no weight chunk
+                      // whose products are 0 * w or discarded (FAR_FEAT_* / FAR_JAC_* below); 0 = all-far tiles run the all-far program
+                      // that streams every chunk (per-lane epilogue)
     // adjoint (MODE 2): upstream gradients in, input / pose gradients out
     const float* g_sdf;    // [n]
     const float* g_grad;   // [n,3]
@@ -351,6 +358,31 @@ constexpr int HB_LEFT_T = chunk_bytes(4, KS_LEFT, true);    // leftover chunk wi
 constexpr int HB_LEFT = chunk_bytes(4, KS_LEFT, false);
 constexpr int HB_G = chunk_bytes(4, 2, true);         // colour lin0: enc(g) columns + the 4 biases
 constexpr int HB_W4ROWS = 3 * TAIL_BYTES;             // adjoint: the three rows of colour lin4, one tail-format KiB each
+
+// ---- the all-far program's weight stream (HONERF_FAR_STREAM, Hand2Args::far_stream; the instance with the shared epilogue) ------------
+// In an all-far tile the B operand of every MFMA over the feature space is the zero fragment (lin0, the lin4 skip columns, colour
+// lin0's feature columns: C += W * 0) or its result is discarded (the Jacobian pass).  The MFMAs run (dense compute) and read their A
+// fragments from LDS as before, but from a RESIDENT chunk: chunk by chunk against build_hand_stream (hn_pack2.hip), the "table"
+// chunks below are exactly those that carry nothing else the tile reads --
+//   feature_block:       per bone two chunks B.chunk(M, .., 4, 4, .., nullptr), HB_BONE, no tail: TABLE.  Then the two leftover chunks,
+//                        whose tail holds lin0's biases (lin4, colour lin0: no tail, but 12 k-step blocks of their own size that the
+//                        code behind the bones acquires, and the fetch of what follows is issued from them): FETCHED, where they are.
+//   feature_rows_T_adj:  4 chunks B.chunk(M, true, .., 1, 16, .., nullptr) of the leftover block, then 4 per bone, HB_BWD, no tail: TABLE.
+//   everything else (the hidden, reverse and colour layers, lin4's hidden part, colour lin0's feature-vector tiles and its enc(g)
+//   chunks with the biases): FETCHED.
+// Of a pass's table chunks the first two are still fetched: the one that is in flight when the pass starts (the code in front of the
+// pass is shared with the other instances) and the one behind it, which becomes the resident chunk.  With the resident chunk in the
+// SECOND buffer of the pass, the first real chunk behind the table lands in the buffer, and leaves ws.phase at the value, that the
+// full stream gives it (an even number of table chunks is skipped), so the code behind a pass is the other instances' code.
+constexpr int FAR_FEAT_TABLE = 2 * N_BONES;        // table chunks of a feature pass
+constexpr int FAR_JAC_TABLE = 4 * (N_BONES + 1);   // ... of the Jacobian pass
+constexpr int FAR_TABLE_FETCHED = 2;               // of each pass's table: the chunk in flight and the resident chunk
+constexpr int FAR_STREAM_SKIPPED = 3 * (FAR_FEAT_TABLE - FAR_TABLE_FETCHED) * HB_BONE + (FAR_JAC_TABLE - FAR_TABLE_FETCHED) * HB_BWD;   // bytes per tile
+static_assert(HB_BONE == 4 * 4 * KS_BYTES && HB_BWD == 16 * KS_BYTES,
+              "a resident chunk is k-step blocks from end to end: every byte an MFMA reads as A is a packed [hi | lo] fragment, never an fp32 tail");
+static_assert((FAR_FEAT_TABLE - FAR_TABLE_FETCHED) % 2 == 0 && (FAR_JAC_TABLE - FAR_TABLE_FETCHED) % 2 == 0,
+              "an even number of chunks is skipped: buffer parity behind the pass is the full stream's");
+static_assert(FAR_STREAM_SKIPPED == 120 * HB_BONE + 86 * HB_BWD, "6.75 MB of the 12.4 MB a tile streams");
 
 struct Bone2 {
     float v, r[3], hh;
@@ -751,8 +783,9 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         // in at least one of the 4 waves (the chunks are shared through LDS, so the skip has to be workgroup-wide),
         // plus bone 0, whose first chunk is always in flight when a pass starts.
         // far (a kernel with the all-far program): no wave of this tile has a live bone, by the kernel's own masks, in a dense launch
-        // that asked for it -- the workgroup runs the tile with the all-far program.  One choice per tile, workgroup-uniform: both
-        // programs pass the same barriers and consume the same weight stream, chunk for chunk.
+        // that asked for it -- the workgroup runs the tile with the all-far program.  One choice per tile, workgroup-uniform: the
+        // programs hand the weight stream to one another in the same state (offset, buffer, the chunk in flight) at every tile end,
+        // and between the passes over the feature space, where the all-far program of HONERF_FAR_STREAM fetches less of it.
         // (A kernel without that program exchanges the masks where it always did, behind the leftover block and for a culled launch alone.)
         unsigned nzw_w = (1u << N_BONES) - 1u;
         bool far = false;
@@ -765,10 +798,22 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             far = nz_any == 0u && a.cull == 0 && a.far_tiles != 0;
         }
         // the tile program from here on: FAR_ = the all-far instance (returns true where a phase-timing build leaves the kernel)
-        // (FAR_ = 2: the all-far instance with the shared epilogue, PhFarShared)
+        // (FAR_ = 2: the all-far instance with the shared epilogue, PhFarShared, and without the table chunks of the stream, FS;
+        //  FAR_ = 1: per-lane epilogue, full stream -- where HONERF_FAR_EPILOGUE or HONERF_FAR_STREAM is 0)
         auto program = [&](auto FAR_) __attribute__((always_inline)) -> bool {
         constexpr bool FAR = decltype(FAR_)::value != 0;
         constexpr bool SH = decltype(FAR_)::value == 2;
+        constexpr bool FS = SH;   // ... which is also the instance that fetches no table chunk (FAR_FEAT_TABLE / FAR_JAC_TABLE above)
+        // a group of MFMAs on the resident chunk: nothing to wait for and no barrier (WStream::hold).  The measurement build keeps the
+        // chunk barrier of the full stream in front of every group: what not fetching buys by itself (profiles/r12)
+        auto resident = [&](const char* buf) {
+#if HN_DBG_FAR_STREAM_BARRIERS
+            (void)ws.template acquire<0>();
+            return buf;
+#else
+            return ws.hold(buf);
+#endif
+        };
         constexpr bool RAW = FAR && HN_DBG_FAR_NO_EPILOGUE;   // (measurement build)
         using PhSp = std::conditional_t<RAW, PhRaw, PhSoftplus>;
         using PhDs = std::conditional_t<RAW, PhRaw, PhDsig>;
@@ -969,7 +1014,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             // bone b's NB chunks (fragments in uh/ul); the last one prefetches the first chunk of bone nb (the next
             // bone that is run; nb == N_BONES: the leftover chunks, which follow the 21 bones in the stream)
             const int base = ws.goff - HB_BONE;   // stream offset of bone 0's first chunk (the chunk in flight)
-            auto step = [&](int nb, const h8(&uh)[4], const h8(&ul)[4], h8(&nh)[4], h8(&nl)[4]) {
+            [[maybe_unused]] auto step = [&](int nb, const h8(&uh)[4], const h8(&ul)[4], h8(&nh)[4], h8(&nl)[4]) {
                 static_for<NB>([&](auto BLK) {
                     constexpr int blk = decltype(BLK)::value;
                     // The next bone's 8 fragment loads are issued one step ahead, from the slot BEHIND this chunk's DMA
@@ -1007,6 +1052,46 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     }
                 });
             };
+            if constexpr (FS) {
+                // The all-far program that fetches no table chunk (FAR_FEAT_TABLE): the 42 bone chunks' MFMAs multiply the zero fragment,
+                // so all but bone 0's two chunks are neither fetched nor waited for.
+                //   entry    bone 0's first chunk is in flight to buffer X (begun by the code in front of the pass); ws.phase = Y
+                //   group 0  acquire: X landed.  Bone 0's second chunk -> Y, its pieces in this group's slots.  MFMAs read X.
+                //   group 1  acquire: Y landed, and every wave has read X for the last time -- so the FIRST LEFTOVER chunk, the next
+                //            chunk of the stream that is needed, goes to X here, at its own offset and at the size the full stream
+                //            fetches it with, and has the whole pass to land.  MFMAs read Y, the resident chunk from here on.
+                //   groups 2 .. 41  read Y.  Nothing is fetched into Y while they run: the next fetch into Y is the second leftover
+                //            chunk's, issued by the code below behind ITS acquire, whose barrier every wave reaches after group 41.
+                //   exit     ws.goff = base + 42 HB_BONE + left_bytes, ws.phase = Y, the first leftover chunk in X: the full stream's
+                //            state behind its 21st bone, so the leftover blocks below are the other instances' code.
+                // The accumulators are those of the full stream, group for group: bone b's chunk blk adds 4 x 4 k-steps of (+-0) to
+                // c[4 blk .. 4 blk + 3] (signed zeros: DESIGN.md 3.1, "HONERF_FAR_STREAM").
+                static_assert(NB == 2 && left_bytes <= HB_BONE && FAR_FEAT_TABLE == NB * N_BONES, "the chunk plan of the 32x32x16 shape");
+                load_bone(N_BONES, fh[0], fl[0]);   // one zero fragment: every bone's and the leftover block's
+                {
+                    // ... and a second one for the lo parts: with ONE run-time value as both B operands, lin0's first two MFMAs of a
+                    // tile (A_hi x hi and A_hi x lo onto accumulators of 0, in groups 0 and 1, outside the loop) are one expression
+                    // and the compiler keeps one of them -- 8 MFMAs short of the dense count per tile
+                    h8 zl = fl[0][0];
+                    asm volatile("" : "+v"(zl));
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) fl[0][s] = zl;
+                }
+                const char* buf = ws.template acquire<0>();
+                ws.template begin_c<HB_BONE>();
+                mma_chunk<4, 4, HB_BONE, PS>(ws, buf, fh[0], fl[0], &c1[0], &c2[0], lane);
+                buf = ws.template acquire<0>();
+                ws.template begin_at_c<HB_BONE>(base + FAR_FEAT_TABLE * HB_BONE);
+                ws.goff += left_bytes - HB_BONE;
+                mma_chunk<4, 4, HB_BONE, PS>(ws, buf, fh[0], fl[0], &c1[HN_EXP_ACC], &c2[HN_EXP_ACC], lane);
+#pragma unroll 1
+                for (int b = 1; b < N_BONES; ++b) {
+                    buf = resident(buf);
+                    mma_chunk<4, 4, 0, PS>(ws, buf, fh[0], fl[0], &c1[0], &c2[0], lane);
+                    buf = resident(buf);
+                    mma_chunk<4, 4, 0, PS>(ws, buf, fh[0], fl[0], &c1[HN_EXP_ACC], &c2[HN_EXP_ACC], lane);
+                }
+            } else {
             load_bone(0, fh[0], fl[0]);
             unsigned rem = nzw & ~1u;
             // two steps per trip with the fragment buffers swapped, NOT one step plus a copy: with a copy at the end
@@ -1034,6 +1119,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     fl[0][s4] = fl[1][s4];
                 }
             }
+            }   // the bone chunks of the full stream
             static_for<NB>([&](auto BLK) {
                 constexpr int blk = decltype(BLK)::value;
                 const char* buf = ws.template acquire<0>();
@@ -1369,7 +1455,53 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) asm volatile("" : "+v"(bh[s]), "+v"(bl[s]), "+a"(ah[s]), "+a"(al[s]));
 #endif
-        {
+        if constexpr (FS) {
+            // The all-far program that fetches no table chunk (FAR_JAC_TABLE): the pass's 88 products are discarded, so all but its
+            // first two chunks are neither fetched nor waited for.
+            //   entry    the pass's first chunk (the leftover block's W0 tile) is in flight to buffer X, begun by the last reverse
+            //            layer; ws.phase = Y
+            //   group 0  acquire: X landed.  The second chunk -> Y, its pieces in this group's slots.  MFMAs read X.
+            //   group 1  acquire: Y landed, every wave has read X for the last time -- so COLOUR LIN0's FIRST CHUNK, the next chunk
+            //            that is needed, goes to X here, at its own offset (88 chunks on from the pass's first) and at the size the
+            //            full stream fetches it with, and has the whole pass to land.  MFMAs read Y, resident from here on.
+            //   groups 2 .. 87  read Y.  The next fetch into Y is colour lin0's second chunk, issued behind that layer's first
+            //            acquire, whose barrier every wave reaches after group 87.
+            //   exit     ws.goff = 89 chunks on from the pass's first, ws.phase = Y, colour lin0's first chunk in X: the full stream's.
+            // Groups, B operands (dz0 and dz4 in turn), accumulators and the sinks of the results are the full stream's.
+            const int jfirst = ws.goff - HB_BWD;   // stream offset of the pass's first chunk (in flight)
+            const char* buf = ws.template acquire<0>();
+            ws.template begin_c<HB_BWD>();
+            {
+                f32x16 L1[2], L2[2];
+                L1[0] = zero16();
+                L2[0] = zero16();
+                mma_tile<16, 0, HB_BWD, PJ>(ws, buf, bh, bl, L1[0], L2[0], lane);
+                buf = ws.template acquire<0>();
+                ws.template begin_at_c<HB_BWD>(jfirst + FAR_JAC_TABLE * HB_BWD);
+                mma_tile<16, 0, HB_BWD, PJ>(ws, buf, ah, al, L1[0], L2[0], lane);
+                L1[1] = zero16();
+                L2[1] = zero16();
+                buf = resident(buf);
+                mma_tile<16, 0, 0, PJ>(ws, buf, bh, bl, L1[1], L2[1], lane);
+                buf = resident(buf);
+                mma_tile<16, 0, 0, PJ>(ws, buf, ah, al, L1[1], L2[1], lane);
+                asm volatile("" ::"v"(L1[0]), "v"(L2[0]), "v"(L1[1]), "v"(L2[1]));   // (the results of MFMAs that run for the dense count)
+            }
+#pragma unroll 1
+            for (int b = 0; b < N_BONES; ++b) {
+                f32x16 G1[2], G2[2];
+                static_for<2>([&](auto U) {
+                    constexpr int u = decltype(U)::value;
+                    G1[u] = zero16();
+                    G2[u] = zero16();
+                    buf = resident(buf);
+                    mma_tile<16, 0, 0, PJ>(ws, buf, bh, bl, G1[u], G2[u], lane);
+                    buf = resident(buf);
+                    mma_tile<16, 0, 0, PJ>(ws, buf, ah, al, G1[u], G2[u], lane);
+                });
+                asm volatile("" ::"v"(G1[0]), "v"(G2[0]), "v"(G1[1]), "v"(G2[1]));
+            }
+        } else {
             // The leftover block first (2 tiles; register 8 (u & 1) + j of tile u >> 1 <-> bone 8 u + j : (r_1 | r_2) h): its
             // per-bone values are parked in the stash and join the bone's own sums below, so that every bone is visited
             // ONCE (coordinates, d/dq, R_b^T) -- as a block behind the bones it cost a second round over all 21 of them,
@@ -1609,7 +1741,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         };   // program
         if constexpr (FAR_ARM && !HN_DBG_FAR_NO_EPILOGUE) {
             const bool out = !far ? program(std::integral_constant<int, 0>{})
-                                  : (a.far_epilogue != 0 ? program(std::integral_constant<int, 2>{}) : program(std::integral_constant<int, 1>{}));
+                                  : ((a.far_epilogue != 0 && a.far_stream != 0) ? program(std::integral_constant<int, 2>{}) : program(std::integral_constant<int, 1>{}));
             if (out) return;
         } else if constexpr (FAR_ARM) {
             if (far ? program(std::integral_constant<int, 1>{}) : program(std::integral_constant<int, 0>{})) return;
@@ -1790,6 +1922,7 @@ int launch_field2_hand(const hn_field* f, const float* pts, int n_pts, const flo
     a.ustash = us_mode == 0 ? 0 : (us_mode == 2 ? USTASH_COLS : (USTASH_COLS | USTASH_SHIFT));
     a.far_tiles = (us_mode == 1 && lo.far_tiles != 0) ? 1 : 0;   // (the all-far tile program goes with the default, packed form)
     a.far_epilogue = lo.far_epilogue != 0 ? 1 : 0;
+    a.far_stream = lo.far_stream != 0 ? 1 : 0;
 #ifdef HN_DEBUG_HOOKS
     {
         const char* e = getenv("HN_DBG");

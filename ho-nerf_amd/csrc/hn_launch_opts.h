@@ -28,6 +28,10 @@ struct FieldLaunchOpts {
     // HONERF_FAR_EPILOGUE (Hand2Args::far_epilogue): 1 = the all-far tile program computes the element-wise epilogues of the SDF
     // network's layers once per row of lanes; 0 = per lane, as the general program does (the same bits)
     int far_epilogue = 1;
+    // HONERF_FAR_STREAM (Hand2Args::far_stream): 1 = the all-far tile program with the shared epilogue neither fetches nor waits for
+    // the weight chunks whose products are 0 * w or discarded (the bone chunks of the three feature passes, the Jacobian pass); 0 =
+    // all-far tiles run the all-far program that streams every chunk, with the per-lane epilogue (the same bits)
+    int far_stream = 1;
 };
 
 // unset or empty -> 1; first character '0' -> 0; '2' -> 2 where the switch has a third form; anything else -> 1
@@ -36,7 +40,7 @@ inline int env_switch(const char* e, bool has_two) {
     return e[0] == '0' ? 0 : ((has_two && e[0] == '2') ? 2 : 1);
 }
 
-// The four environment switches, read ONCE per C-ABI call, where that call builds its options (a setenv between two calls takes
+// The five environment switches, read ONCE per C-ABI call, where that call builds its options (a setenv between two calls takes
 // effect).  live_first (optional): HONERF_LIVE_FIRST, the single-field render's own switch: 0 = off; 1 = on for launches the field
 // kernel treats as long; 2 = on at every size.
 inline FieldLaunchOpts resolve_launch_opts(int* live_first = nullptr) {
@@ -44,6 +48,7 @@ inline FieldLaunchOpts resolve_launch_opts(int* live_first = nullptr) {
     o.uniform_stash = env_switch(getenv("HONERF_UNIFORM_STASH"), true);
     o.far_tiles = env_switch(getenv("HONERF_FAR_TILES"), false);
     o.far_epilogue = env_switch(getenv("HONERF_FAR_EPILOGUE"), false);
+    o.far_stream = env_switch(getenv("HONERF_FAR_STREAM"), false);
     if (live_first != nullptr) *live_first = env_switch(getenv("HONERF_LIVE_FIRST"), true);
     return o;
 }

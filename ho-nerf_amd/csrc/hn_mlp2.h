@@ -298,6 +298,20 @@ struct WStream {
         stamp(3);
         return lds + (phase ^ 1) * CHUNK_MAX;
     }
+    // A RESIDENT chunk (the all-far hand program's passes over the feature space, hn_field2_hand.hip): the buffer that the last
+    // acquire() returned is read again by the next group of MFMAs, nothing having been fetched for that group.  No wait and no
+    // barrier -- nothing lands, and the rule a fetch has to keep is unchanged: it goes into buffer X only behind a barrier that every
+    // wave reaches after its last read of X, so while a chunk is resident the fetches in flight go to the OTHER buffer and the next
+    // acquire() is the barrier that frees this one.  What remains is the compiler's side of acquire(): the memory clobber, so that the
+    // group's ds_read_b128 are issued again and no A fragment of an earlier group is kept in registers or hoisted out of a loop.  The
+    // stamps keep the per-chunk record of the timing builds in step.
+    __device__ __forceinline__ const char* hold(const char* buf) {
+        stamp(1);
+        stamp(2);
+        asm volatile("" ::: "memory");
+        stamp(3);
+        return buf;
+    }
 };
 constexpr int MAX_PIECES_PER_WAVE = 9;
 
