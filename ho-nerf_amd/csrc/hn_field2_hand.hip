@@ -49,6 +49,13 @@
 #define HN_DBG_FAR_STREAM_BARRIERS 0   // 1 (measurement only, the same results): the all-far program that fetches no table chunk keeps the full
                                        // stream's s_waitcnt vmcnt(0) + s_barrier in front of every chunk group all the same
 #endif
+// The two steps of "discarded products keep their operands in registers" (profiles/r13), for same-source A/B builds:
+#ifndef HN_FAR_JAC_ZERO
+#define HN_FAR_JAC_ZERO 1   // the all-far program without table chunks: the Jacobian pass's discarded products take the zero fragment as B
+#endif
+#ifndef HN_FAR_HOLD_A
+#define HN_FAR_HOLD_A 1     // ... and its resident groups take one k-step's A fragments from registers, loaded once per pass (mma_held)
+#endif
 #ifndef HN_DEFER_STASH
 #define HN_DEFER_STASH 0   // 1: the fp32 activation tiles of the hidden layers go to the stash one chunk late (to_regs_hold): measured, no gain
 #endif
@@ -361,9 +368,10 @@ constexpr int HB_W4ROWS = 3 * TAIL_BYTES;             // adjoint: the three rows
 
 // ---- the all-far program's weight stream (HONERF_FAR_STREAM, Hand2Args::far_stream; the instance with the shared epilogue) ------------
 // In an all-far tile the B operand of every MFMA over the feature space is the zero fragment (lin0, the lin4 skip columns, colour
-// lin0's feature columns: C += W * 0) or its result is discarded (the Jacobian pass).  The MFMAs run (dense compute) and read their A
-// fragments from LDS as before, but from a RESIDENT chunk: chunk by chunk against build_hand_stream (hn_pack2.hip), the "table"
-// chunks below are exactly those that carry nothing else the tile reads --
+// lin0's feature columns: C += W * 0) or its result is discarded (the Jacobian pass).  The MFMAs run (dense compute), but on a
+// RESIDENT chunk -- and, HN_FAR_HOLD_A, on ONE k-step of it that is read into registers once per pass (mma_held in hn_mlp2.h); the
+// Jacobian pass's B operand is the zero fragment too (HN_FAR_JAC_ZERO).  Chunk by chunk against build_hand_stream (hn_pack2.hip), the
+// "table" chunks below are exactly those that carry nothing else the tile reads --
 //   feature_block:       per bone two chunks B.chunk(M, .., 4, 4, .., nullptr), HB_BONE, no tail: TABLE.  Then the two leftover chunks,
 //                        whose tail holds lin0's biases (lin4, colour lin0: no tail, but 12 k-step blocks of their own size that the
 //                        code behind the bones acquires, and the fetch of what follows is issued from them): FETCHED, where they are.
@@ -814,6 +822,14 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             return ws.hold(buf);
 #endif
         };
+        // ... and one whose A fragments are held in registers (HN_FAR_HOLD_A, mma_held): no memory clobber either
+        [[maybe_unused]] auto resident_held = [&]() {
+#if HN_DBG_FAR_STREAM_BARRIERS
+            (void)ws.template acquire<0>();
+#else
+            ws.held();
+#endif
+        };
         constexpr bool RAW = FAR && HN_DBG_FAR_NO_EPILOGUE;   // (measurement build)
         using PhSp = std::conditional_t<RAW, PhRaw, PhSoftplus>;
         using PhDs = std::conditional_t<RAW, PhRaw, PhDsig>;
@@ -1081,15 +1097,29 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 ws.template begin_c<HB_BONE>();
                 mma_chunk<4, 4, HB_BONE, PS>(ws, buf, fh[0], fl[0], &c1[0], &c2[0], lane);
                 buf = ws.template acquire<0>();
+                // HN_FAR_HOLD_A: groups 2 .. 41 read nothing.  Their A operand is k-step 0 of Y's first tile, in registers from here
+                // (behind the acquire that made Y resident) to the end of the pass.  The same bits come out: every byte of a table
+                // chunk is a packed finite fp16 value (the static_assert at FAR_STREAM_SKIPPED), a finite value times the zero
+                // fragment is +-0 whichever weight it is, and +-0 onto an accumulator that is not -0 leaves it as it was
+                // ("Signed zeros").
+                [[maybe_unused]] HeldA held;
+                if constexpr (HN_FAR_HOLD_A) held = held_load(buf);
                 ws.template begin_at_c<HB_BONE>(base + FAR_FEAT_TABLE * HB_BONE);
                 ws.goff += left_bytes - HB_BONE;
                 mma_chunk<4, 4, HB_BONE, PS>(ws, buf, fh[0], fl[0], &c1[HN_EXP_ACC], &c2[HN_EXP_ACC], lane);
 #pragma unroll 1
                 for (int b = 1; b < N_BONES; ++b) {
-                    buf = resident(buf);
-                    mma_chunk<4, 4, 0, PS>(ws, buf, fh[0], fl[0], &c1[0], &c2[0], lane);
-                    buf = resident(buf);
-                    mma_chunk<4, 4, 0, PS>(ws, buf, fh[0], fl[0], &c1[HN_EXP_ACC], &c2[HN_EXP_ACC], lane);
+                    if constexpr (HN_FAR_HOLD_A) {
+                        resident_held();
+                        mma_held<4, 4, PS>(ws, held, fh[0], fl[0], &c1[0], &c2[0]);
+                        resident_held();
+                        mma_held<4, 4, PS>(ws, held, fh[0], fl[0], &c1[HN_EXP_ACC], &c2[HN_EXP_ACC]);
+                    } else {
+                        buf = resident(buf);
+                        mma_chunk<4, 4, 0, PS>(ws, buf, fh[0], fl[0], &c1[0], &c2[0], lane);
+                        buf = resident(buf);
+                        mma_chunk<4, 4, 0, PS>(ws, buf, fh[0], fl[0], &c1[HN_EXP_ACC], &c2[HN_EXP_ACC], lane);
+                    }
                 }
             } else {
             load_bone(0, fh[0], fl[0]);
@@ -1442,6 +1472,10 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         //      bh/bl), then W4[:, 256:]^T dz4 (reloaded into ah/al)
         // G = W0^T dz0 + W4[:, 256:]^T dz4 accumulated per tile (chunks alternate between the two matrices),
         // so that the features and the Jacobian are visited once
+        // (the all-far program without table chunks discards the pass's products and multiplies the zero fragment instead, HN_FAR_JAC_ZERO
+        //  below: dz0 and dz4 are dead behind the reverse sweep, and nothing is reloaded or moved here)
+        constexpr bool JZ = FS && HN_FAR_JAC_ZERO;
+        if constexpr (!JZ) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) sh.frag_load(HS_DZ4 * SLOT_BYTES, s, ah[s], al[s]);
         // dz0 (parked in AGPRs by the last reverse layer) is the B operand of 44 chunks: back into VGPRs once, here
@@ -1455,6 +1489,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) asm volatile("" : "+v"(bh[s]), "+v"(bl[s]), "+a"(ah[s]), "+a"(al[s]));
 #endif
+        }
         if constexpr (FS) {
             // The all-far program that fetches no table chunk (FAR_JAC_TABLE): the pass's 88 products are discarded, so all but its
             // first two chunks are neither fetched nor waited for.
@@ -1468,37 +1503,72 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             //            acquire, whose barrier every wave reaches after group 87.
             //   exit     ws.goff = 89 chunks on from the pass's first, ws.phase = Y, colour lin0's first chunk in X: the full stream's.
             // Groups, B operands (dz0 and dz4 in turn), accumulators and the sinks of the results are the full stream's.
+            // HN_FAR_JAC_ZERO: ... except the B operands, which are the zero fragment in every group: the last products of the tile that
+            // still switched the matrix pipe on sample-dependent values for nothing.  Two run-time zeros, hi and lo, as in the feature
+            // passes (with one, the first MFMAs of a group's two accumulators are one expression).
+            // HN_FAR_HOLD_A: groups 2 .. 87 read nothing.  Their A operand is k-step 0 of Y, in registers from the acquire that made Y
+            // resident to the end of the pass -- every byte of a table chunk is a packed finite fp16 value (the static_assert at
+            // FAR_STREAM_SKIPPED), and no result of the pass is kept.  Every iteration of the bone loop is then the same expression
+            // on the same operands: mma_held launders its A fragment per group, and the disassembly keeps 88 x 48 MFMAs
+            // (tests/test_far_hold_isa.py).
+            h8 zh[16], zl[16];
+            if constexpr (JZ) {
+                h8 z;
+#pragma unroll
+                for (int jj = 0; jj < 8; ++jj) z[jj] = (_Float16)0.f;
+                asm volatile("" : "+v"(z));
+                h8 z2 = z;
+                asm volatile("" : "+v"(z2));
+#pragma unroll
+                for (int s = 0; s < 16; ++s) {
+                    zh[s] = z;
+                    zl[s] = z2;
+                }
+            }
+            auto pick = [](auto& zero, auto& real) -> auto& {
+                if constexpr (JZ)
+                    return zero;
+                else
+                    return real;
+            };
+            const auto &b0h = pick(zh, bh), &b0l = pick(zl, bl), &b4h = pick(zh, ah), &b4l = pick(zl, al);   // "dz0", "dz4"
             const int jfirst = ws.goff - HB_BWD;   // stream offset of the pass's first chunk (in flight)
             const char* buf = ws.template acquire<0>();
             ws.template begin_c<HB_BWD>();
+            [[maybe_unused]] HeldA held;
+            // a tile on the resident chunk: its "dz0" group, then its "dz4" group
+            auto resident_tile = [&](f32x16& g1, f32x16& g2) {
+                g1 = zero16();
+                g2 = zero16();
+                if constexpr (HN_FAR_HOLD_A) {
+                    resident_held();
+                    mma_held<1, 16, PJ>(ws, held, b0h, b0l, &g1, &g2);
+                    resident_held();
+                    mma_held<1, 16, PJ>(ws, held, b4h, b4l, &g1, &g2);
+                } else {
+                    buf = resident(buf);
+                    mma_tile<16, 0, 0, PJ>(ws, buf, b0h, b0l, g1, g2, lane);
+                    buf = resident(buf);
+                    mma_tile<16, 0, 0, PJ>(ws, buf, b4h, b4l, g1, g2, lane);
+                }
+            };
             {
                 f32x16 L1[2], L2[2];
                 L1[0] = zero16();
                 L2[0] = zero16();
-                mma_tile<16, 0, HB_BWD, PJ>(ws, buf, bh, bl, L1[0], L2[0], lane);
+                mma_tile<16, 0, HB_BWD, PJ>(ws, buf, b0h, b0l, L1[0], L2[0], lane);
                 buf = ws.template acquire<0>();
+                if constexpr (HN_FAR_HOLD_A) held = held_load(buf);
                 ws.template begin_at_c<HB_BWD>(jfirst + FAR_JAC_TABLE * HB_BWD);
-                mma_tile<16, 0, HB_BWD, PJ>(ws, buf, ah, al, L1[0], L2[0], lane);
-                L1[1] = zero16();
-                L2[1] = zero16();
-                buf = resident(buf);
-                mma_tile<16, 0, 0, PJ>(ws, buf, bh, bl, L1[1], L2[1], lane);
-                buf = resident(buf);
-                mma_tile<16, 0, 0, PJ>(ws, buf, ah, al, L1[1], L2[1], lane);
+                mma_tile<16, 0, HB_BWD, PJ>(ws, buf, b4h, b4l, L1[0], L2[0], lane);
+                resident_tile(L1[1], L2[1]);
                 asm volatile("" ::"v"(L1[0]), "v"(L2[0]), "v"(L1[1]), "v"(L2[1]));   // (the results of MFMAs that run for the dense count)
             }
 #pragma unroll 1
             for (int b = 0; b < N_BONES; ++b) {
                 f32x16 G1[2], G2[2];
-                static_for<2>([&](auto U) {
-                    constexpr int u = decltype(U)::value;
-                    G1[u] = zero16();
-                    G2[u] = zero16();
-                    buf = resident(buf);
-                    mma_tile<16, 0, 0, PJ>(ws, buf, bh, bl, G1[u], G2[u], lane);
-                    buf = resident(buf);
-                    mma_tile<16, 0, 0, PJ>(ws, buf, ah, al, G1[u], G2[u], lane);
-                });
+                resident_tile(G1[0], G2[0]);
+                resident_tile(G1[1], G2[1]);
                 asm volatile("" ::"v"(G1[0]), "v"(G2[0]), "v"(G1[1]), "v"(G2[1]));
             }
         } else {

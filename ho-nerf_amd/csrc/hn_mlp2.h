@@ -312,6 +312,13 @@ struct WStream {
         stamp(3);
         return buf;
     }
+    // ... and a group that reads NOTHING: its A fragments are held in registers (mma_held below).  No clobber either; the stamps alone,
+    // so that a timing build still records one chunk start per group.
+    __device__ __forceinline__ void held() {
+        stamp(1);
+        stamp(2);
+        stamp(3);
+    }
 };
 constexpr int MAX_PIECES_PER_WAVE = 9;
 
@@ -655,6 +662,37 @@ __device__ __forceinline__ void mma_chunk(WStream& ws, const char* buf, const h8
         // (slot indices continue over the tiles of the chunk: block k of tile t is slot base 3 (t KS + k))
         auto slot_t = [&](auto Q_) { slot(std::integral_constant<int, decltype(Q_)::value + 3 * t * KS>{}); };
         mma_block<k, 0, PASSES>(ah[s % 3], al[s % 3], xh, xl, c1[t], c2[t], slot_t);
+    });
+    ws.stamp(4);
+}
+
+// The same group of NT tiles x KS k-steps -- the same 3 NT KS MFMAs in the same order onto the same accumulators -- with ONE k-step's
+// A fragments, [hi | lo] in 8 VGPRs, HELD in registers for every block of the group: no LDS read, no DMA piece.  For groups whose
+// products are +-0 or discarded whatever finite A they multiply (the resident groups of the all-far hand program).
+// A group whose other operands and accumulator seeds do not change from one group to the next is otherwise ONE expression to the
+// compiler -- the MFMA builtin is pure -- and is hoisted out of a loop or merged with its twin: the hi fragment, which the first
+// MFMA of either accumulator chain reads, is laundered per group, so every group is issued.
+struct HeldA {
+    h8 hi, lo;
+};
+__device__ __forceinline__ HeldA held_load(const char* buf) {
+    const char* const lbuf = buf + lane_x16();
+    HeldA w;
+    w.hi = *reinterpret_cast<const h8*>(lbuf);
+    w.lo = *reinterpret_cast<const h8*>(lbuf + 1024);
+    return w;
+}
+template <int NT, int KS, int PASSES = 3, int NX>
+__device__ __forceinline__ void mma_held(WStream& ws, HeldA& w, const h8 (&xh)[NX], const h8 (&xl)[NX], f32x16* c1, f32x16* c2) {
+    static_assert(KS <= NX, "k-step range");
+    static_assert(!S16 || KS % 2 == 0, "the 16x16x32 shape consumes k-steps in pairs");
+    asm volatile("" : "+v"(w.hi));
+    auto slot = [&](auto) { __builtin_amdgcn_sched_barrier(0); };
+    static_for<NT * KS>([&](auto S) {
+        constexpr int s = decltype(S)::value;
+        constexpr int t = s / KS, k = s % KS;
+        if constexpr (k == 0 && NT > 1) ws.stamp(5);   // (the stamps of mma_chunk; NT == 1: those of mma_tile)
+        mma_block<k, 0, PASSES>(w.hi, w.lo, xh, xl, c1[t], c2[t], slot);
     });
     ws.stamp(4);
 }

@@ -13,7 +13,7 @@ cd /tmp
 ARGS="$R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-culled --no-fitting --no-training --no-c1 --no-f16"
 LIM=${PASS_LIMIT:-300}
 timeout -k 10 $LIM rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ARGS > $OUT/stats.log 2>&1 || { echo "kernel-trace pass failed ($?)"; tail -5 $OUT/stats.log; exit 1; }
-for P in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA"; do
+for P in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA" "SQ_INSTS_LDS"; do
   N=$(echo $P | tr ' ' '_')
   timeout -k 10 $LIM rocprofv3 --pmc $P --output-format csv -d $OUT/pmc_$N -- python3 $ARGS > $OUT/pmc_$N.log 2>&1 || { echo "--pmc $P pass failed ($?)"; tail -5 $OUT/pmc_$N.log; exit 1; }
 done
