@@ -56,6 +56,11 @@
 #ifndef HN_FAR_HOLD_A
 #define HN_FAR_HOLD_A 1     // ... and its resident groups take one k-step's A fragments from registers, loaded once per pass (mma_held)
 #endif
+#ifndef HN_FAR_REV_HELD
+#define HN_FAR_REV_HELD 1   // ... and, where HN_FAR_JAC_ZERO leaves dz0 and dz4 dead, the reverse sweep is a discarded pass of the same kind: two
+                            // chunks fetched, 54 groups on held A fragments, the zero fragment as B, no epilogues, no a_l / dz7 / dz4 kept
+                            // (profiles/r14)
+#endif
 #ifndef HN_DEFER_STASH
 #define HN_DEFER_STASH 0   // 1: the fp32 activation tiles of the hidden layers go to the stash one chunk late (to_regs_hold): measured, no gain
 #endif
@@ -382,8 +387,13 @@ constexpr int HB_W4ROWS = 3 * TAIL_BYTES;             // adjoint: the three rows
 // pass is shared with the other instances) and the one behind it, which becomes the resident chunk.  With the resident chunk in the
 // SECOND buffer of the pass, the first real chunk behind the table lands in the buffer, and leaves ws.phase at the value, that the
 // full stream gives it (an even number of table chunks is skipped), so the code behind a pass is the other instances' code.
+// The REVERSE SWEEP (HN_FAR_REV_HELD) is a pass of the same kind although its chunks are no table: with the Jacobian pass on zero
+// fragments (HN_FAR_JAC_ZERO) nothing reads dz6 .. dz0, so the sweep's 56 products (W7^T .. W1^T, 8 tiles each, one HB_BWD chunk per
+// tile, no tail) are discarded as well.  Its first two chunks are fetched, the other 54 are not; its groups multiply the zero fragment
+// and run no epilogue, and the forward layers keep neither a1 .. a7 nor the seed dz7 for it.
 constexpr int FAR_FEAT_TABLE = 2 * N_BONES;        // table chunks of a feature pass
 constexpr int FAR_JAC_TABLE = 4 * (N_BONES + 1);   // ... of the Jacobian pass
+constexpr int FAR_REV_TABLE = 7 * 8;               // chunks of the reverse sweep, discarded where HN_FAR_JAC_ZERO and HN_FAR_REV_HELD
 constexpr int FAR_TABLE_FETCHED = 2;               // of each pass's table: the chunk in flight and the resident chunk
 constexpr int FAR_STREAM_SKIPPED = 3 * (FAR_FEAT_TABLE - FAR_TABLE_FETCHED) * HB_BONE + (FAR_JAC_TABLE - FAR_TABLE_FETCHED) * HB_BWD;   // bytes per tile
 static_assert(HB_BONE == 4 * 4 * KS_BYTES && HB_BWD == 16 * KS_BYTES,
@@ -391,6 +401,9 @@ static_assert(HB_BONE == 4 * 4 * KS_BYTES && HB_BWD == 16 * KS_BYTES,
 static_assert((FAR_FEAT_TABLE - FAR_TABLE_FETCHED) % 2 == 0 && (FAR_JAC_TABLE - FAR_TABLE_FETCHED) % 2 == 0,
               "an even number of chunks is skipped: buffer parity behind the pass is the full stream's");
 static_assert(FAR_STREAM_SKIPPED == 120 * HB_BONE + 86 * HB_BWD, "6.75 MB of the 12.4 MB a tile streams");
+constexpr int FAR_REV_SKIPPED = (FAR_REV_TABLE - FAR_TABLE_FETCHED) * HB_BWD;   // bytes per tile, HN_FAR_REV_HELD
+static_assert((FAR_REV_TABLE - FAR_TABLE_FETCHED) % 2 == 0 && FAR_REV_SKIPPED == 54 * HB_BWD,
+              "an even number of the sweep's chunks is skipped too: 1.77 MB of the 5.6 MB that were left");
 
 struct Bone2 {
     float v, r[3], hh;
@@ -812,6 +825,10 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         constexpr bool FAR = decltype(FAR_)::value != 0;
         constexpr bool SH = decltype(FAR_)::value == 2;
         constexpr bool FS = SH;   // ... which is also the instance that fetches no table chunk (FAR_FEAT_TABLE / FAR_JAC_TABLE above)
+        // ... and whose reverse sweep is a discarded pass (FAR_REV_TABLE): nothing is kept for it, so the forward layers' epilogues have no
+        // slot of the image to store a_l to
+        constexpr bool RH = FS && HN_FAR_JAC_ZERO && HN_FAR_REV_HELD;
+        [[maybe_unused]] constexpr auto far_dst = [](int slot) { return RH ? DST_NONE : slot; };
         // a group of MFMAs on the resident chunk: nothing to wait for and no barrier (WStream::hold).  The measurement build keeps the
         // chunk barrier of the full stream in front of every group: what not fetching buys by itself (profiles/r12)
         auto resident = [&](const char* buf) {
@@ -1226,12 +1243,12 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             }
             feature_pass(I2{}, BTrue{}, c1, c2, std::integral_constant<int, HB_LEFT_T>{}, std::integral_constant<int, HB_HID>{}, IPF{});
             if constexpr (SH)
-                block_epilogue_far(I8t{}, c1, c2, PhFarShared<0, HS_A1 + 0, 0>{shf.img}, to_regs(ah, al));
+                block_epilogue_far(I8t{}, c1, c2, PhFarShared<0, far_dst(HS_A1 + 0), 0>{shf.img}, to_regs(ah, al));
             else
                 block_epilogue(I8t{}, c1, c2, PhSp{}, to_regs_keep(ah, al, HS_A1 + 0));
         }
         if constexpr (SH) {
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, HS_A1 + 1, 0>{shf.img}, to_regs(bh, bl), no_store);   // lin1
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, far_dst(HS_A1 + 1), 0>{shf.img}, to_regs(bh, bl), no_store);   // lin1
         } else {
 #if HN_DEFER_STASH
         run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 1));   // lin1
@@ -1240,7 +1257,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
 #endif
         }
         if constexpr (SH) {
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<0, HS_A1 + 2, 0>{shf.img}, to_regs(ah, al), no_store);   // lin2
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<0, far_dst(HS_A1 + 2), 0>{shf.img}, to_regs(ah, al), no_store);   // lin2
         } else {
 #if HN_DEFER_STASH
         run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSp{}, to_regs_hold(ah, al), store_tile(HS_A1 + 2));   // lin2
@@ -1252,7 +1269,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         // through the stash -- 32 KB written and read back at once per tile, an HBM round trip of ~10 000 cycles in front
         // of lin4 in the in-kernel stamps.)
         if constexpr (SH) {
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, HS_A1 + 3, 0>{shf.img}, to_regs(bh, bl), no_store);   // lin3
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, far_dst(HS_A1 + 3), 0>{shf.img}, to_regs(bh, bl), no_store);   // lin3
         } else {
 #if HN_DEFER_STASH
         run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 3));   // lin3
@@ -1275,12 +1292,12 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             });
             feature_pass(I2{}, BFalse{}, c1, c2, std::integral_constant<int, HB_LEFT>{}, std::integral_constant<int, HB_HID>{}, IPF{});
             if constexpr (SH)
-                block_epilogue_far(I8t{}, c1, c2, PhFarShared<0, HS_A1 + 4, 0>{shf.img}, to_regs(ah, al));
+                block_epilogue_far(I8t{}, c1, c2, PhFarShared<0, far_dst(HS_A1 + 4), 0>{shf.img}, to_regs(ah, al));
             else
                 block_epilogue(I8t{}, c1, c2, PhSp{}, to_regs_keep(ah, al, HS_A1 + 4));
         }
         if constexpr (SH) {
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, HS_A1 + 5, 0>{shf.img}, to_regs(bh, bl), no_store);   // lin5
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, far_dst(HS_A1 + 5), 0>{shf.img}, to_regs(bh, bl), no_store);   // lin5
         } else {
 #if HN_DEFER_STASH
         run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 5));   // lin5
@@ -1289,7 +1306,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
 #endif
         }
         if constexpr (SH) {
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<0, HS_A1 + 6, 0>{shf.img}, to_regs(ah, al), no_store);   // lin6
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<0, far_dst(HS_A1 + 6), 0>{shf.img}, to_regs(ah, al), no_store);   // lin6
         } else {
 #if HN_DEFER_STASH
         run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSp{}, to_regs_hold(ah, al), store_tile(HS_A1 + 6));   // lin6
@@ -1327,16 +1344,18 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                         sdf_acc1 = fmaf(w8.v[i], st.v[i], sdf_acc1);
                     else
                         sdf_acc = fmaf(w8.v[i], st.v[i], sdf_acc);
-                    dz[i] = dsoftplus_from_act(st.v[i]) * w8.v[i] * BWD_SCALE;
+                    if constexpr (!RH) dz[i] = dsoftplus_from_act(st.v[i]) * w8.v[i] * BWD_SCALE;
                 }
                 if (FULL) {
                     bh[2 * t] = st.hi[0];   // a8 feeds lin8
                     bl[2 * t] = st.lo[0];
                     bh[2 * t + 1] = st.hi[1];
                     bl[2 * t + 1] = st.lo[1];
+                    if constexpr (!RH) {   // (the seed of a sweep that is discarded is not formed)
                     Frags f;
                     split_tile(dz, f.hi[0], f.lo[0], f.hi[1], f.lo[1]);
                     stash_frags(HS_DZ7)(T, f);
+                    }
                     if constexpr (ADJ) {
                         sh.tile_store(HS_A8, t, st.vec());
                         sh.tile_store(HS_DZ + 7, t, dz);
@@ -1405,8 +1424,10 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             };
 #endif
         };
+        if constexpr (!RH) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) sh.frag_load(HS_DZ7 * SLOT_BYTES, s, ah[s], al[s]);
+        }
         // (adjoint mode: every dz_l also goes to the stash as an fp32 tile, slot HS_DZ + l)
         auto to_regs_t = [&](h8(&oh)[16], h8(&ol)[16], int tile_slot) {
             return [&oh, &ol, tile_slot, &sh, &park](auto T, EpiState& st, const auto&) {
@@ -1423,6 +1444,78 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 return NoData{};
             };
         };
+        // the zero fragments of the all-far program's discarded passes: two run-time zeros, hi and lo (with one, the first MFMAs of a
+        // group's two accumulators are one expression)
+        [[maybe_unused]] h8 zh[16], zl[16];
+        [[maybe_unused]] auto far_zeros = [&]() {
+            h8 z;
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) z[jj] = (_Float16)0.f;
+            asm volatile("" : "+v"(z));
+            h8 z2 = z;
+            asm volatile("" : "+v"(z2));
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                zh[s] = z;
+                zl[s] = z2;
+            }
+        };
+        if constexpr (RH) {
+            // The all-far program whose Jacobian pass multiplies zero fragments (HN_FAR_JAC_ZERO): d sdf / d p is a run-time +0 by
+            // construction, nothing reads dz6 .. dz0, and the sweep's 56 products (FAR_REV_TABLE) are discarded like that pass's.
+            //   entry    the sweep's first chunk (W7^T, tile 0) is in flight to buffer X, begun by lin8; ws.phase = Y
+            //   group 0  acquire: X landed.  The second chunk -> Y, its pieces in this group's slots.  MFMAs read X.
+            //   group 1  acquire: Y landed, every wave has read X for the last time -- so the JACOBIAN PASS's FIRST CHUNK, the next chunk
+            //            that is needed, goes to X here, at its own offset (56 chunks on from the sweep's first) and at the size the
+            //            full stream fetches it with, and has the whole sweep to land.  k-step 0 of Y goes into registers; MFMAs read Y.
+            //   groups 2 .. 55  read nothing (HN_FAR_HOLD_A; without it they read Y, resident).  The next fetch into Y is the Jacobian
+            //            pass's second chunk, issued behind that pass's first acquire, whose barrier every wave reaches after group 55.
+            //   exit     ws.goff = 57 chunks on from the sweep's first, ws.phase = Y, the Jacobian pass's first chunk in X: the full
+            //            stream's state behind W1^T, so the pass below is untouched.
+            // Every group is one tile of the full sweep -- 16 k-steps onto zeroed accumulators, PH MFMAs per product -- with the zero
+            // fragment as B (two run-time zeros, hi and lo, as in the other passes) and its results sunk: no epilogue, no sigma' from a
+            // stashed a_l, no fragments of dz parked or stashed.  A reverse chunk is packed finite fp16 from end to end (the static_assert at
+            // FAR_STREAM_SKIPPED), so the held k-step is finite whichever layer's it is.  mma_held launders its A fragment per group:
+            // the disassembly keeps the sweep's 56 x 16 PH MFMAs (tests/test_far_hold_isa.py).
+            far_zeros();   // (the Jacobian pass below multiplies the same two)
+            const int rfirst = ws.goff - HB_BWD;   // stream offset of the sweep's first chunk (in flight)
+            f32x16 r1, r2;
+            // the results of MFMAs that run for the dense count.  A single-pass product never touches its second accumulator, which is
+            // then not sunk: its 16 registers of zeros per group cost k_field2_hand_f16<1> 22 more spilled registers, twelve of them
+            // reloaded inside the general program's Jacobian loop (profiles/r14)
+            auto sink = [](const f32x16& c1, const f32x16& c2) {
+                if constexpr (PH == 3)
+                    asm volatile("" ::"v"(c1), "v"(c2));
+                else
+                    asm volatile("" ::"v"(c1));
+            };
+            const char* buf = ws.template acquire<0>();
+            ws.template begin_c<HB_BWD>();
+            r1 = zero16();
+            r2 = zero16();
+            mma_tile<16, 0, HB_BWD, PH>(ws, buf, zh, zl, r1, r2, lane);
+            sink(r1, r2);
+            buf = ws.template acquire<0>();
+            [[maybe_unused]] HeldA held;
+            if constexpr (HN_FAR_HOLD_A) held = held_load(buf);
+            ws.template begin_at_c<HB_BWD>(rfirst + FAR_REV_TABLE * HB_BWD);
+            r1 = zero16();
+            r2 = zero16();
+            mma_tile<16, 0, HB_BWD, PH>(ws, buf, zh, zl, r1, r2, lane);
+            sink(r1, r2);
+            static_for<FAR_REV_TABLE - FAR_TABLE_FETCHED>([&](auto) {
+                r1 = zero16();
+                r2 = zero16();
+                if constexpr (HN_FAR_HOLD_A) {
+                    resident_held();
+                    mma_held<1, 16, PH>(ws, held, zh, zl, &r1, &r2);
+                } else {
+                    buf = resident(buf);
+                    mma_tile<16, 0, 0, PH>(ws, buf, zh, zl, r1, r2, lane);
+                }
+                sink(r1, r2);
+            });
+        } else {
         if constexpr (SH)
         run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 6>{shf.img}, to_regs_t(bh, bl, HS_DZ + 6), no_store);   // W7^T -> dz6
         else
@@ -1466,6 +1559,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 0>{shf.img}, to_regs_t(bh, bl, HS_DZ + 0), no_store);   // W1^T -> dz0
         else
         run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 0), PhDs{}, to_regs_t(bh, bl, HS_DZ + 0), no_store);   // W1^T -> dz0
+        }   // the real sweep
 
         if ((HN_DBG(a) >> 8) == 7) return true;   // phase timing aid
         // ---- d sdf / d features contracted with the encoding Jacobian, bone by bone: first W0^T dz0 (dz0 is in
@@ -1511,20 +1605,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             // FAR_STREAM_SKIPPED), and no result of the pass is kept.  Every iteration of the bone loop is then the same expression
             // on the same operands: mma_held launders its A fragment per group, and the disassembly keeps 88 x 48 MFMAs
             // (tests/test_far_hold_isa.py).
-            h8 zh[16], zl[16];
-            if constexpr (JZ) {
-                h8 z;
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) z[jj] = (_Float16)0.f;
-                asm volatile("" : "+v"(z));
-                h8 z2 = z;
-                asm volatile("" : "+v"(z2));
-#pragma unroll
-                for (int s = 0; s < 16; ++s) {
-                    zh[s] = z;
-                    zl[s] = z2;
-                }
-            }
+            if constexpr (JZ && !RH) far_zeros();
             auto pick = [](auto& zero, auto& real) -> auto& {
                 if constexpr (JZ)
                     return zero;
