@@ -18,51 +18,8 @@
 #define HN_MFMA16 HN_HAND_EVAL_MFMA16   // the evaluation kernels (MODE 0, 1); the adjoint translation unit keeps 32x32x16
 #endif
 #include "hn_mlp2.h"
-#ifndef HN_FEAT_ACQUIRE_VISIBLE
-#define HN_FEAT_ACQUIRE_VISIBLE true
-#endif
-#ifndef HN_FEAT_LOADS_BEHIND
-#define HN_FEAT_LOADS_BEHIND 1
-#endif
-#ifndef HN_JAC_VARIANT
-#define HN_JAC_VARIANT 2
-#endif
-#ifndef HN_PARK_AGPR
-#define HN_PARK_AGPR 1
-#endif
-#ifndef HN_EXP_ACC
-#define HN_EXP_ACC 4
-#endif
 #ifndef HN_FAR_TILES   // 1: the full evaluation kernels carry the all-far tile program (FarStash below); 0: the general program alone
-#if (defined(HN_STASH_HALF) && HN_STASH_HALF) || (defined(HN_DBG_NO_FEAT_LOADS) && HN_DBG_NO_FEAT_LOADS)
-#define HN_FAR_TILES 0   // (the measurement builds are builds of the general program)
-#else
 #define HN_FAR_TILES 1
-#endif
-#endif
-#ifndef HN_DBG_FAR_NO_EPILOGUE
-#define HN_DBG_FAR_NO_EPILOGUE 0   // 1 (measurement only, WRONG results): the all-far program's 15 SDF-side tile epilogues (lin0..lin7, the seven
-                                   // layers of the reverse sweep) issue no phase work: the next layer's fragments are conversions of the raw
-                                   // accumulators and a_l is not read back -- an upper bound on what the shared epilogue can buy (profiles/r11)
-#endif
-#ifndef HN_DBG_FAR_STREAM_BARRIERS
-#define HN_DBG_FAR_STREAM_BARRIERS 0   // 1 (measurement only, the same results): the all-far program that fetches no table chunk keeps the full
-                                       // stream's s_waitcnt vmcnt(0) + s_barrier in front of every chunk group all the same
-#endif
-// The two steps of "discarded products keep their operands in registers" (profiles/r13), for same-source A/B builds:
-#ifndef HN_FAR_JAC_ZERO
-#define HN_FAR_JAC_ZERO 1   // the all-far program without table chunks: the Jacobian pass's discarded products take the zero fragment as B
-#endif
-#ifndef HN_FAR_HOLD_A
-#define HN_FAR_HOLD_A 1     // ... and its resident groups take one k-step's A fragments from registers, loaded once per pass (mma_held)
-#endif
-#ifndef HN_FAR_REV_HELD
-#define HN_FAR_REV_HELD 1   // ... and, where HN_FAR_JAC_ZERO leaves dz0 and dz4 dead, the reverse sweep is a discarded pass of the same kind: two
-                            // chunks fetched, 54 groups on held A fragments, the zero fragment as B, no epilogues, no a_l / dz7 / dz4 kept
-                            // (profiles/r14)
-#endif
-#ifndef HN_DEFER_STASH
-#define HN_DEFER_STASH 0   // 1: the fp32 activation tiles of the hidden layers go to the stash one chunk late (to_regs_hold): measured, no gain
 #endif
 
 namespace hn {
@@ -263,30 +220,22 @@ struct FarStash {
 
 // ---- the shared epilogue of the all-far program (HONERF_FAR_EPILOGUE, Hand2Args::far_epilogue) ---------------------------------------
 // In an all-far tile the 16 values that lane (j, h) holds of an output tile do not depend on j, so the element-wise epilogue of the SDF
-// network's layers (softplus forward, g sigma' in the reverse sweep) and the fp16 split behind it are the same 32 results computed by
-// 32 lanes each.  Here they are computed ONCE per row of 16 lanes, one element per lane, and come back to every lane through LDS:
+// network's forward layers (softplus; the program's reverse sweep is a discarded pass and has none) and the fp16 split behind it
+// are the same 32 results computed by 32 lanes each.  Here they are computed ONCE per row of 16 lanes, one element per lane, and
+// come back to every lane through LDS:
 //   calls 0..7   every lane forms z = c2 * inv + c1, the packed fma of pair_phase, and keeps element e = j & 15 of the 16: a tree of 15
 //                v_cndmask_b32 on the four low bits of the lane number, the masks being constants in scalar registers (the first form
 //                sent z through LDS -- the j == 0 lanes stored a line of 16 z per half, every lane read one element back: four
-//                ds_write_b128 of the whole wave per tile, and the reverse sweep came out SLOWER than per lane in the in-kernel stamps);
-//   call 10      KIND 1: lane (j, h) reads element e of a_l straight from the image;
+//                ds_write_b128 of the whole wave per tile, and came out SLOWER than per lane in the in-kernel stamps);
+//   call 10      the offset of element e = j & 15 of half h within a tile of the image's layout (what call 20 stores through);
 //   calls 16..19 one element through pair_phase's operations in scalar form (v_mul, v_exp, v_add, v_log, v_max, v_fma: the packed
 //                forms round each half as these do);
-//   call 20      the fp32 result to the image cell where tile_store would have put it (DST: an a_l slot; the lanes j and j ^ 16
-//                store the same bits to the same cell), or back to FAR_Z (DST_LINE: lin7, whose `fin` reads all 16);
+//   call 20      LINE (lin7, whose `fin` reads all 16): the fp32 result to its element's cell of the line FAR_Z (the lanes j and j ^ 16
+//                store the same bits to the same cell); the other layers' a_l are kept nowhere: nothing reads them;
 //   calls 21, 22 split_pair_hi / split_pair_lo's instructions on the one value, the two halves to FAR_FRAG;
 //   call 28      every lane reads the tile's four fragments, four broadcast ds_read_b128.
 // A wave's LDS operations complete in order, so nothing but program order stands between a line's store and its read.  The calls sit
 // in the MFMA slots of the next tile like pair_phase's (Epi::run); the lane offsets are formed where they are used (lane_x16()).
-// pd.t is the tile's index within the layer.
-struct FarTile {
-    int t;
-};
-struct FarActT {
-    f32x16 v;
-    int t;
-};
-constexpr int DST_NONE = -1, DST_LINE = -2;
 // lane bit B set ? b : a -- one v_cndmask_b32 whose mask is a constant (no v_cmp, nothing live across the tile)
 template <int B>
 __device__ __forceinline__ float lane_bit_select(float a, float b) {
@@ -295,19 +244,18 @@ __device__ __forceinline__ float lane_bit_select(float a, float b) {
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(M));
     return r;
 }
-template <int KIND, int DST, int ACT>   // KIND: 0 softplus, 1 PhDsig; DST: slot of the fp32 results; ACT (KIND 1): slot of a_l
+template <bool LINE>   // softplus; LINE: the fp32 results go to the line FAR_Z
 struct PhFarShared {
-    static_assert(KIND == 0 || KIND == 1, "softplus or g sigma'");
     static constexpr bool own_calls = true;
-    static constexpr int kind = KIND;
-    static constexpr bool branchy = KIND == 0 ? HN_BRANCHY_FWD : HN_BRANCHY_REV;
+    static constexpr int kind = 0;
+    static constexpr bool branchy = HN_BRANCHY_FWD;
     char* img;
     float z, x, v;       // carried from call to call of one tile
     float g[8];          // the select tree of calls 0..7
     unsigned hp, lp;
     char* pe;
     template <int C, bool FRAGS, typename PD>
-    __device__ __forceinline__ void call(EpiState& st, const PD& pd) {
+    __device__ __forceinline__ void call(EpiState& st, const PD&) {
         if constexpr (C < 8) {
             constexpr int i0 = 2 * C, i1 = 2 * C + 1;
             const f32x2 c1 = {st.c1[i0], st.c1[i1]}, c2 = {st.c2[i0], st.c2[i1]};
@@ -318,23 +266,20 @@ struct PhFarShared {
             if constexpr ((C & 3) == 3) g[C - 3] = lane_bit_select<2>(g[C - 3], g[C - 1]);
             if constexpr (C == 7) z = lane_bit_select<3>(g[0], g[4]);
         } else if constexpr (C == 10) {
+            // (formed in every tile, kept or not: lane_x16() is an asm volatile, and its three instructions are part of the device code
+            //  as it stands)
             const int l16 = lane_x16();   // 512 h + 16 j -> 32 (e >> 2) + 16 h + 4 (e & 3), e = j & 15
             pe = img + (((l16 & 0xC0) >> 1) | ((l16 >> 5) & 16) | ((l16 >> 2) & 12));
-            if constexpr (KIND == 1) x = *reinterpret_cast<const float*>(pe + (ACT * SLOT_BYTES >> USTASH_SHIFT) + pd.t * 128);
         } else if constexpr (C == 16) {
-            x = KIND == 0 ? z * K100_ : x * -K100_;
+            x = z * K100_;
         } else if constexpr (C == 17) {
-            x = KIND == 0 ? __builtin_amdgcn_exp2f(-fabsf(x)) : __builtin_amdgcn_exp2f(x);
+            x = __builtin_amdgcn_exp2f(-fabsf(x));
         } else if constexpr (C == 18) {
-            if constexpr (KIND == 0) x = __builtin_amdgcn_logf(x + 1.f);
+            x = __builtin_amdgcn_logf(x + 1.f);
         } else if constexpr (C == 19) {
-            if constexpr (KIND == 0)
-                v = x * C100_ + fmaxf(z, 0.f);
-            else
-                v = z - z * x;
+            v = x * C100_ + fmaxf(z, 0.f);
         } else if constexpr (C == 20) {
-            if constexpr (DST == DST_LINE) *reinterpret_cast<float*>(pe + FAR_Z) = v;
-            if constexpr (DST >= 0) *reinterpret_cast<float*>(pe + (DST * SLOT_BYTES >> USTASH_SHIFT) + pd.t * 128) = v;
+            if constexpr (LINE) *reinterpret_cast<float*>(pe + FAR_Z) = v;
         } else if constexpr (C == 21) {
             if constexpr (FRAGS) {
                 float r;   // (the instructions of split_pair_hi / split_pair_lo, both members of the pair being this value)
@@ -373,10 +318,10 @@ constexpr int HB_W4ROWS = 3 * TAIL_BYTES;             // adjoint: the three rows
 
 // ---- the all-far program's weight stream (HONERF_FAR_STREAM, Hand2Args::far_stream; the instance with the shared epilogue) ------------
 // In an all-far tile the B operand of every MFMA over the feature space is the zero fragment (lin0, the lin4 skip columns, colour
-// lin0's feature columns: C += W * 0) or its result is discarded (the Jacobian pass).  The MFMAs run (dense compute), but on a
-// RESIDENT chunk -- and, HN_FAR_HOLD_A, on ONE k-step of it that is read into registers once per pass (mma_held in hn_mlp2.h); the
-// Jacobian pass's B operand is the zero fragment too (HN_FAR_JAC_ZERO).  Chunk by chunk against build_hand_stream (hn_pack2.hip), the
-// "table" chunks below are exactly those that carry nothing else the tile reads --
+// lin0's feature columns: C += W * 0) or its result is discarded (the Jacobian pass).  The MFMAs run (dense compute), but on ONE
+// k-step of a chunk that is read into registers once per pass (mma_held in hn_mlp2.h); the Jacobian pass's B operand is the zero
+// fragment too.  Chunk by chunk against build_hand_stream (hn_pack2.hip), the "table" chunks below are exactly those that carry
+// nothing else the tile reads --
 //   feature_block:       per bone two chunks B.chunk(M, .., 4, 4, .., nullptr), HB_BONE, no tail: TABLE.  Then the two leftover chunks,
 //                        whose tail holds lin0's biases (lin4, colour lin0: no tail, but 12 k-step blocks of their own size that the
 //                        code behind the bones acquires, and the fetch of what follows is issued from them): FETCHED, where they are.
@@ -384,24 +329,24 @@ constexpr int HB_W4ROWS = 3 * TAIL_BYTES;             // adjoint: the three rows
 //   everything else (the hidden, reverse and colour layers, lin4's hidden part, colour lin0's feature-vector tiles and its enc(g)
 //   chunks with the biases): FETCHED.
 // Of a pass's table chunks the first two are still fetched: the one that is in flight when the pass starts (the code in front of the
-// pass is shared with the other instances) and the one behind it, which becomes the resident chunk.  With the resident chunk in the
+// pass is shared with the other instances) and the one behind it, whose first k-step is the held one.  With that chunk in the
 // SECOND buffer of the pass, the first real chunk behind the table lands in the buffer, and leaves ws.phase at the value, that the
 // full stream gives it (an even number of table chunks is skipped), so the code behind a pass is the other instances' code.
-// The REVERSE SWEEP (HN_FAR_REV_HELD) is a pass of the same kind although its chunks are no table: with the Jacobian pass on zero
-// fragments (HN_FAR_JAC_ZERO) nothing reads dz6 .. dz0, so the sweep's 56 products (W7^T .. W1^T, 8 tiles each, one HB_BWD chunk per
-// tile, no tail) are discarded as well.  Its first two chunks are fetched, the other 54 are not; its groups multiply the zero fragment
-// and run no epilogue, and the forward layers keep neither a1 .. a7 nor the seed dz7 for it.
+// The REVERSE SWEEP is a pass of the same kind although its chunks are no table: with the Jacobian pass on zero fragments nothing
+// reads dz6 .. dz0, so the sweep's 56 products (W7^T .. W1^T, 8 tiles each, one HB_BWD chunk per tile, no tail) are discarded as
+// well.  Its first two chunks are fetched, the other 54 are not; its groups multiply the zero fragment and run no epilogue, and the
+// forward layers keep neither a1 .. a7 nor the seed dz7 for it.  (discarded_pass in the kernel is the protocol of all three.)
 constexpr int FAR_FEAT_TABLE = 2 * N_BONES;        // table chunks of a feature pass
 constexpr int FAR_JAC_TABLE = 4 * (N_BONES + 1);   // ... of the Jacobian pass
-constexpr int FAR_REV_TABLE = 7 * 8;               // chunks of the reverse sweep, discarded where HN_FAR_JAC_ZERO and HN_FAR_REV_HELD
-constexpr int FAR_TABLE_FETCHED = 2;               // of each pass's table: the chunk in flight and the resident chunk
+constexpr int FAR_REV_TABLE = 7 * 8;               // chunks of the reverse sweep, discarded with the Jacobian pass's
+constexpr int FAR_TABLE_FETCHED = 2;               // of each pass's table: the chunk in flight and the one whose k-step 0 is held
 constexpr int FAR_STREAM_SKIPPED = 3 * (FAR_FEAT_TABLE - FAR_TABLE_FETCHED) * HB_BONE + (FAR_JAC_TABLE - FAR_TABLE_FETCHED) * HB_BWD;   // bytes per tile
 static_assert(HB_BONE == 4 * 4 * KS_BYTES && HB_BWD == 16 * KS_BYTES,
-              "a resident chunk is k-step blocks from end to end: every byte an MFMA reads as A is a packed [hi | lo] fragment, never an fp32 tail");
+              "a table chunk is k-step blocks from end to end: every byte an MFMA reads as A is a packed [hi | lo] fragment, never an fp32 tail");
 static_assert((FAR_FEAT_TABLE - FAR_TABLE_FETCHED) % 2 == 0 && (FAR_JAC_TABLE - FAR_TABLE_FETCHED) % 2 == 0,
               "an even number of chunks is skipped: buffer parity behind the pass is the full stream's");
 static_assert(FAR_STREAM_SKIPPED == 120 * HB_BONE + 86 * HB_BWD, "6.75 MB of the 12.4 MB a tile streams");
-constexpr int FAR_REV_SKIPPED = (FAR_REV_TABLE - FAR_TABLE_FETCHED) * HB_BWD;   // bytes per tile, HN_FAR_REV_HELD
+constexpr int FAR_REV_SKIPPED = (FAR_REV_TABLE - FAR_TABLE_FETCHED) * HB_BWD;   // bytes per tile
 static_assert((FAR_REV_TABLE - FAR_TABLE_FETCHED) % 2 == 0 && FAR_REV_SKIPPED == 54 * HB_BWD,
               "an even number of the sweep's chunks is skipped too: 1.77 MB of the 5.6 MB that were left");
 
@@ -819,37 +764,13 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             far = nz_any == 0u && a.cull == 0 && a.far_tiles != 0;
         }
         // the tile program from here on: FAR_ = the all-far instance (returns true where a phase-timing build leaves the kernel)
-        // (FAR_ = 2: the all-far instance with the shared epilogue, PhFarShared, and without the table chunks of the stream, FS;
+        // (FAR_ = 2, LEAN: the all-far instance with the shared epilogue, PhFarShared, that fetches no table chunk of the stream
+        //  (FAR_FEAT_TABLE / FAR_JAC_TABLE above) and whose reverse sweep is a discarded pass (FAR_REV_TABLE): nothing is kept for the
+        //  sweep, so the forward layers' epilogues have no slot of the image to store a_l to;
         //  FAR_ = 1: per-lane epilogue, full stream -- where HONERF_FAR_EPILOGUE or HONERF_FAR_STREAM is 0)
         auto program = [&](auto FAR_) __attribute__((always_inline)) -> bool {
         constexpr bool FAR = decltype(FAR_)::value != 0;
-        constexpr bool SH = decltype(FAR_)::value == 2;
-        constexpr bool FS = SH;   // ... which is also the instance that fetches no table chunk (FAR_FEAT_TABLE / FAR_JAC_TABLE above)
-        // ... and whose reverse sweep is a discarded pass (FAR_REV_TABLE): nothing is kept for it, so the forward layers' epilogues have no
-        // slot of the image to store a_l to
-        constexpr bool RH = FS && HN_FAR_JAC_ZERO && HN_FAR_REV_HELD;
-        [[maybe_unused]] constexpr auto far_dst = [](int slot) { return RH ? DST_NONE : slot; };
-        // a group of MFMAs on the resident chunk: nothing to wait for and no barrier (WStream::hold).  The measurement build keeps the
-        // chunk barrier of the full stream in front of every group: what not fetching buys by itself (profiles/r12)
-        auto resident = [&](const char* buf) {
-#if HN_DBG_FAR_STREAM_BARRIERS
-            (void)ws.template acquire<0>();
-            return buf;
-#else
-            return ws.hold(buf);
-#endif
-        };
-        // ... and one whose A fragments are held in registers (HN_FAR_HOLD_A, mma_held): no memory clobber either
-        [[maybe_unused]] auto resident_held = [&]() {
-#if HN_DBG_FAR_STREAM_BARRIERS
-            (void)ws.template acquire<0>();
-#else
-            ws.held();
-#endif
-        };
-        constexpr bool RAW = FAR && HN_DBG_FAR_NO_EPILOGUE;   // (measurement build)
-        using PhSp = std::conditional_t<RAW, PhRaw, PhSoftplus>;
-        using PhDs = std::conditional_t<RAW, PhRaw, PhDsig>;
+        constexpr bool LEAN = decltype(FAR_)::value == 2;
         const unsigned nz = FAR ? 0u : nz_w;
         unsigned nzw = FAR ? (1u << N_BONES) - 1u : nzw_w;
         auto& sh = [&]() -> auto& {
@@ -917,11 +838,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         // Finished output fragments are parked in AGPRs until the next layer reads them: the layer that produces them
         // already holds its 128 input-fragment registers, the epilogue state and the pre-loaded side data in VGPRs, and
         // with the outputs there too the allocator goes to scratch memory inside the MFMA loops.
-        auto park = [](h8& a0, h8& a1, h8& a2, h8& a3) {
-#if HN_PARK_AGPR
-            asm volatile("" : "+a"(a0), "+a"(a1), "+a"(a2), "+a"(a3));
-#endif
-        };
+        auto park = [](h8& a0, h8& a1, h8& a2, h8& a3) { asm volatile("" : "+a"(a0), "+a"(a1), "+a"(a2), "+a"(a3)); };
         auto no_pre = [](auto, const char*) { return NoData{}; };
         auto no_store = [](auto, const auto&) {};
         auto stash_frags = [&](int stash_slot) {
@@ -931,8 +848,14 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 sh.frag_store(stash_slot * SLOT_BYTES, 2 * t + 1, f.hi[1], f.lo[1]);
             };
         };
-        auto to_regs = [&](h8(&oh)[16], h8(&ol)[16]) {
-            return [&oh, &ol, &park](auto T, EpiState& st, const auto&) {
+        // The finisher of a layer whose output fragments go to oh / ol.  KEEP_: whether the tile's fp32 values go to stash slot `slot`
+        // as well -- KeepFull: in the full evaluation (a1..a7, for the reverse sweep; the stores cost power, not issue slots or waits:
+        // DESIGN.md 3.1, round 4), KeepAdj: in the adjoint modes (the tape), KeepNo: never
+        using KeepNo = std::integral_constant<bool, false>;
+        using KeepFull = std::integral_constant<bool, FULL>;
+        using KeepAdj = std::integral_constant<bool, ADJ>;
+        auto to_regs_keep = [&](auto KEEP_, h8(&oh)[16], h8(&ol)[16], int slot) {
+            return [&oh, &ol, slot, &sh, &park](auto T, EpiState& st, const auto&) {
                 constexpr int t = decltype(T)::value;
                 asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
                 oh[2 * t] = st.hi[0];
@@ -940,76 +863,59 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 oh[2 * t + 1] = st.hi[1];
                 ol[2 * t + 1] = st.lo[1];
                 park(oh[2 * t], ol[2 * t], oh[2 * t + 1], ol[2 * t + 1]);
+                (void)slot;
+                (void)sh;
+                if constexpr (decltype(KEEP_)::value) sh.tile_store(slot, t, st.vec());
                 return NoData{};
             };
         };
-        // The same with the fp32 tile handed to run_layer's deferred `store` instead of being stored here: the store of tile t is
-        // then issued right BEHIND the next chunk's barrier, a whole chunk ahead of the barrier after it (-DHN_DEFER_STASH=1).
-        // Round-4 A/B on the C2 frame: with the a1..a7 stores REMOVED (wrong gradients, -DHN_STASH_HALF=2) the kernel
-        // runs 250.5 -> 226.5 ms -- in the SAME number of cycles (in-kernel stamps) at a higher clock, 1932 -> 2052 MHz: the stores
-        // cost power, not issue slots or waits; issued one chunk late (this form): no change; as half as many bytes (fp16,
-        // -DHN_STASH_HALF=1, not parity-preserving): no change either.
-        [[maybe_unused]] auto to_regs_hold = [&](h8(&oh)[16], h8(&ol)[16]) {
-            return [&oh, &ol, &park](auto T, EpiState& st, const auto&) {
-                constexpr int t = decltype(T)::value;
-                asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
-                oh[2 * t] = st.hi[0];
-                ol[2 * t] = st.lo[0];
-                oh[2 * t + 1] = st.hi[1];
-                ol[2 * t + 1] = st.lo[1];
-                park(oh[2 * t], ol[2 * t], oh[2 * t + 1], ol[2 * t + 1]);
-                return Act{st.vec()};
-            };
-        };
-        [[maybe_unused]] auto store_tile = [&](int stash_slot) {
-            return [stash_slot, &sh](auto T, const Act& held) {
-                if (FULL) sh.tile_store(stash_slot, decltype(T)::value, held.v);
-            };
-        };
-        auto to_regs_keep = [&](h8(&oh)[16], h8(&ol)[16], int stash_slot) {
-            return [&oh, &ol, stash_slot, &sh, &park](auto T, EpiState& st, const auto&) {
-                constexpr int t = decltype(T)::value;
-                asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
-                oh[2 * t] = st.hi[0];
-                ol[2 * t] = st.lo[0];
-                oh[2 * t + 1] = st.hi[1];
-                ol[2 * t + 1] = st.lo[1];
-                park(oh[2 * t], ol[2 * t], oh[2 * t + 1], ol[2 * t + 1]);
-#if defined(HN_STASH_HALF) && HN_STASH_HALF
-                if (FULL) {   // (measurement builds: 1 = half-width values, see Stash::tile_store_half; 2 = no store at all: wrong gradients,
-                              //  the issue-slot cost of the stores alone)
-                    if constexpr (MODE == 1) {
-                        if (HN_STASH_HALF == 1) sh.tile_store_half(stash_slot, t, st.vec());
-                    } else
-                        sh.tile_store(stash_slot, t, st.vec());
-                }
-#else
-                if (FULL) sh.tile_store(stash_slot, t, st.vec());
-#endif
-                return NoData{};
-            };
+        auto to_regs = [&](h8(&oh)[16], h8(&ol)[16]) { return to_regs_keep(KeepNo{}, oh, ol, 0); };
+
+        // ---- the chunk protocol of a discarded pass (the lean all-far program; FAR_FEAT_TABLE / FAR_REV_TABLE / FAR_JAC_TABLE above) ----
+        // A pass of TABLE chunks whose products are +-0 or discarded fetches its first two chunks, CB bytes each, and none of the others:
+        //   entry    the pass's first chunk is in flight to buffer X (begun by the code in front of the pass); ws.phase = Y
+        //   group 0  acquire: X landed.  The second chunk -> Y, its pieces in this group's slots.  MFMAs read X.
+        //   group 1  acquire: Y landed, and every wave has read X for the last time -- so the next chunk of the stream that is NEEDED,
+        //            the one TABLE chunks on from the pass's first, goes to X here, at its own offset and at the size the full stream
+        //            fetches it with (CB; where the chunk is shorter the caller's group 1 corrects ws.goff), and has the whole pass to
+        //            land.  k-step 0 of Y goes into registers: the HeldA returned.  MFMAs read Y.
+        //   the other groups  are the caller's, ws.held() + mma_held on that k-step: they read nothing.  Nothing is fetched into Y
+        //            while they run: the next fetch into Y is issued behind the first acquire after the pass, whose barrier every
+        //            wave reaches after the pass's last group.
+        //   exit     ws.goff = TABLE + 1 chunks on from the pass's first, ws.phase = Y, the next needed chunk in X: the full stream's
+        //            state behind the pass, so the code behind a pass is the other instances' code.
+        // group(G, buf) issues the MFMAs of group G = 0, 1 on the chunk at buf, with the DMA pieces of a CB-byte fetch in their slots.
+        // A chunk of these passes is packed finite fp16 from end to end (the static_assert at FAR_STREAM_SKIPPED), so the held k-step
+        // is finite, and a finite value times the zero fragment is +-0 whichever weight it is.
+        [[maybe_unused]] auto discarded_pass = [&](auto CB_, auto TABLE_, auto&& group) __attribute__((always_inline)) -> HeldA {
+            constexpr int CB = decltype(CB_)::value, TABLE = decltype(TABLE_)::value;
+            const int first = ws.goff - CB;   // stream offset of the pass's first chunk (in flight)
+            const char* buf = ws.template acquire<0>();
+            ws.template begin_c<CB>();
+            group(std::integral_constant<int, 0>{}, buf);
+            buf = ws.template acquire<0>();
+            HeldA held = held_load(buf);
+            ws.template begin_at_c<CB>(first + TABLE * CB);
+            group(std::integral_constant<int, 1>{}, buf);
+            return held;
         };
 
         // ---- NB blocks of 4 output tiles over the feature space: per bone NB chunks (4 tiles x 4 k-steps each)
         //      sharing the bone's fragments, then NB leftover chunks (4 tiles x 3 k-steps [+ tail: the 4 biases,
         //      added here when BIAS]).  c1/c2[4 blk + ti] += W[tile, features] * feat.  Bone b+1's fragments are
         //      loaded while bone b's MFMAs run.
-#ifndef HN_DBG_NO_FEAT_LOADS
-#define HN_DBG_NO_FEAT_LOADS 0   // 1 (measurement only, WRONG results): the feature passes never read the bones' fragments back from the stash -- an
-                                 // upper bound on what reading them twice instead of four times could buy (round 5, profiles/r05/README.md)
-#endif
-        auto bone_loads = [&](int b) { return !FAR && !HN_DBG_NO_FEAT_LOADS && (USTASH || b >= N_BONES || ((nz >> b) & 1u)); };   // load_bone issues its 8 loads
+        auto bone_loads = [&](int b) { return !FAR && (USTASH || b >= N_BONES || ((nz >> b) & 1u)); };   // load_bone issues its 8 loads
         auto load_bone = [&](int b, h8(&oh)[4], h8(&ol)[4]) {
             if constexpr (USTASH && !FAR) {
                 // No branch here: the fragments of a bone that is not live are LOADED from beyond the descriptor's range, which moves
                 // nothing and returns zeros (as f32_load_z).  As the two arms of a branch, the zero arm of the first feature pass's
                 // load_bone(0) comes out behind the loads with waits for them in front of its moves (tests/test_abi.py's static check
                 // of the ISA), and a uniform wave, which always takes it, then waits for the weight pieces in flight.
-                const unsigned live = HN_DBG_NO_FEAT_LOADS ? 0u : (((nz | (1u << N_BONES)) >> b) & 1u);
+                const unsigned live = ((nz | (1u << N_BONES)) >> b) & 1u;
                 const int beyond = (int)((live ^ 1u) << 30);
 #pragma unroll
                 for (int s = 0; s < 4; ++s) sh.frag_load(feat_base, 4 * b + s, oh[s], ol[s], beyond);
-            } else if (!FAR && !HN_DBG_NO_FEAT_LOADS && (b >= N_BONES || ((nz >> b) & 1u))) {
+            } else if (!FAR && (b >= N_BONES || ((nz >> b) & 1u))) {
                 if constexpr (!FAR) {
 #pragma unroll
                     for (int s = 0; s < 4; ++s) sh.frag_load(feat_base, 4 * b + s, oh[s], ol[s]);
@@ -1043,6 +949,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             constexpr int PS = decltype(PS_)::value;   // MFMA passes per product
             constexpr int left_bytes = decltype(LB_)::value, next_after = decltype(NA_)::value;   // chunk sizes: constants
             constexpr bool BIAS = decltype(BIAS_)::value;
+            constexpr int ACC_BLK = 4;   // accumulator tiles per block
             h8 fh[2][4], fl[2][4];
             // bone b's NB chunks (fragments in uh/ul); the last one prefetches the first chunk of bone nb (the next
             // bone that is run; nb == N_BONES: the leftover chunks, which follow the 21 bones in the stream)
@@ -1056,49 +963,45 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     // more to come back from HBM.  The drains are the s_waitcnt builtin (VISIBLE): with the opaque asm
                     // form the compiler guards this bone's first use with counted waits that only the loads issued
                     // AFTER it can satisfy (in-kernel stamps: blk-0 chunks 3 000 - 5 000 cycles against 2 400).
-                    const bool ahead = blk == 1 && NB == 2 && HN_FEAT_LOADS_BEHIND && bone_loads(nb);
-                    const char* buf = ahead ? ws.template acquire<8, HN_FEAT_ACQUIRE_VISIBLE>() : ws.template acquire<0, HN_FEAT_ACQUIRE_VISIBLE>();
-                    if constexpr (blk == 0 && !(NB == 2 && HN_FEAT_LOADS_BEHIND)) load_bone(nb, nh, nl);   // nb == 21: the leftover blocks 84..86
+                    const bool ahead = blk == 1 && NB == 2 && bone_loads(nb);
+                    const char* buf = ahead ? ws.template acquire<8, true>() : ws.template acquire<0, true>();
+                    if constexpr (blk == 0 && NB != 2) load_bone(nb, nh, nl);   // nb == 21: the leftover blocks 84..86
                     if constexpr (blk + 1 < NB) {
                         ws.template begin_c<HB_BONE>();
-                        if constexpr (blk == 0 && NB == 2 && HN_FEAT_LOADS_BEHIND)
-                            mma_chunk<4, 4, HB_BONE, PS>(ws, buf, uh, ul, &c1[HN_EXP_ACC * blk], &c2[HN_EXP_ACC * blk], lane, [&]() { load_bone(nb, nh, nl); });
+                        if constexpr (blk == 0 && NB == 2)
+                            mma_chunk<4, 4, HB_BONE, PS>(ws, buf, uh, ul, &c1[ACC_BLK * blk], &c2[ACC_BLK * blk], lane, [&]() { load_bone(nb, nh, nl); });
                         else
-                            mma_chunk<4, 4, HB_BONE, PS>(ws, buf, uh, ul, &c1[HN_EXP_ACC * blk], &c2[HN_EXP_ACC * blk], lane);   // one pipeline over the 16 blocks
+                            mma_chunk<4, 4, HB_BONE, PS>(ws, buf, uh, ul, &c1[ACC_BLK * blk], &c2[ACC_BLK * blk], lane);   // one pipeline over the 16 blocks
                     } else if constexpr (left_bytes <= HB_BONE) {
                         // the first leftover chunk (nb == 21) is shorter than a bone chunk: fetched at the bone size all
                         // the same (the size stays a constant; 7 - 8 KiB of the following chunk come along unused)
                         ws.goff = base + nb * (NB * HB_BONE);
                         ws.template begin_c<HB_BONE>();
                         if (nb >= N_BONES) ws.goff += left_bytes - HB_BONE;
-                        mma_chunk<4, 4, HB_BONE, PS>(ws, buf, uh, ul, &c1[HN_EXP_ACC * blk], &c2[HN_EXP_ACC * blk], lane);
+                        mma_chunk<4, 4, HB_BONE, PS>(ws, buf, uh, ul, &c1[ACC_BLK * blk], &c2[ACC_BLK * blk], lane);
                     } else {
                         // (16x16x32: the leftover chunk has four k-steps and is the longer one when it carries a tail)
                         ws.goff = base + nb * (NB * HB_BONE);
                         if (nb < N_BONES) {
                             ws.template begin_c<HB_BONE>();
-                            mma_chunk<4, 4, HB_BONE, PS>(ws, buf, uh, ul, &c1[HN_EXP_ACC * blk], &c2[HN_EXP_ACC * blk], lane);
+                            mma_chunk<4, 4, HB_BONE, PS>(ws, buf, uh, ul, &c1[ACC_BLK * blk], &c2[ACC_BLK * blk], lane);
                         } else {
                             ws.template begin_c<left_bytes>();
-                            mma_chunk<4, 4, left_bytes, PS>(ws, buf, uh, ul, &c1[HN_EXP_ACC * blk], &c2[HN_EXP_ACC * blk], lane);
+                            mma_chunk<4, 4, left_bytes, PS>(ws, buf, uh, ul, &c1[ACC_BLK * blk], &c2[ACC_BLK * blk], lane);
                         }
                     }
                 });
             };
-            if constexpr (FS) {
+            if constexpr (LEAN) {
                 // The all-far program that fetches no table chunk (FAR_FEAT_TABLE): the 42 bone chunks' MFMAs multiply the zero fragment,
-                // so all but bone 0's two chunks are neither fetched nor waited for.
-                //   entry    bone 0's first chunk is in flight to buffer X (begun by the code in front of the pass); ws.phase = Y
-                //   group 0  acquire: X landed.  Bone 0's second chunk -> Y, its pieces in this group's slots.  MFMAs read X.
-                //   group 1  acquire: Y landed, and every wave has read X for the last time -- so the FIRST LEFTOVER chunk, the next
-                //            chunk of the stream that is needed, goes to X here, at its own offset and at the size the full stream
-                //            fetches it with, and has the whole pass to land.  MFMAs read Y, the resident chunk from here on.
-                //   groups 2 .. 41  read Y.  Nothing is fetched into Y while they run: the next fetch into Y is the second leftover
-                //            chunk's, issued by the code below behind ITS acquire, whose barrier every wave reaches after group 41.
-                //   exit     ws.goff = base + 42 HB_BONE + left_bytes, ws.phase = Y, the first leftover chunk in X: the full stream's
-                //            state behind its 21st bone, so the leftover blocks below are the other instances' code.
+                // so all but bone 0's two chunks are neither fetched nor waited for (discarded_pass: 42 groups, the chunk needed
+                // next is the FIRST LEFTOVER chunk, shorter than a bone chunk; the second leftover chunk's fetch into Y is issued by
+                // the code below behind ITS acquire).  On exit ws.goff = base + 42 HB_BONE + left_bytes: the full stream's state
+                // behind its 21st bone, so the leftover blocks below are the other instances' code.
                 // The accumulators are those of the full stream, group for group: bone b's chunk blk adds 4 x 4 k-steps of (+-0) to
-                // c[4 blk .. 4 blk + 3] (signed zeros: DESIGN.md 3.1, "HONERF_FAR_STREAM").
+                // c[4 blk .. 4 blk + 3] (signed zeros: DESIGN.md 3.1, "HONERF_FAR_STREAM").  The same bits come out with the held
+                // k-step (k-step 0 of the first tile of bone 0's second chunk) as A: +-0 onto an accumulator that is not -0 leaves
+                // it as it was ("Signed zeros").
                 static_assert(NB == 2 && left_bytes <= HB_BONE && FAR_FEAT_TABLE == NB * N_BONES, "the chunk plan of the 32x32x16 shape");
                 load_bone(N_BONES, fh[0], fl[0]);   // one zero fragment: every bone's and the leftover block's
                 {
@@ -1110,33 +1013,17 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
 #pragma unroll
                     for (int s = 0; s < 4; ++s) fl[0][s] = zl;
                 }
-                const char* buf = ws.template acquire<0>();
-                ws.template begin_c<HB_BONE>();
-                mma_chunk<4, 4, HB_BONE, PS>(ws, buf, fh[0], fl[0], &c1[0], &c2[0], lane);
-                buf = ws.template acquire<0>();
-                // HN_FAR_HOLD_A: groups 2 .. 41 read nothing.  Their A operand is k-step 0 of Y's first tile, in registers from here
-                // (behind the acquire that made Y resident) to the end of the pass.  The same bits come out: every byte of a table
-                // chunk is a packed finite fp16 value (the static_assert at FAR_STREAM_SKIPPED), a finite value times the zero
-                // fragment is +-0 whichever weight it is, and +-0 onto an accumulator that is not -0 leaves it as it was
-                // ("Signed zeros").
-                [[maybe_unused]] HeldA held;
-                if constexpr (HN_FAR_HOLD_A) held = held_load(buf);
-                ws.template begin_at_c<HB_BONE>(base + FAR_FEAT_TABLE * HB_BONE);
-                ws.goff += left_bytes - HB_BONE;
-                mma_chunk<4, 4, HB_BONE, PS>(ws, buf, fh[0], fl[0], &c1[HN_EXP_ACC], &c2[HN_EXP_ACC], lane);
+                HeldA held = discarded_pass(std::integral_constant<int, HB_BONE>{}, std::integral_constant<int, FAR_FEAT_TABLE>{}, [&](auto BLK, const char* buf) {
+                    constexpr int blk = decltype(BLK)::value;
+                    if constexpr (blk == 1) ws.goff += left_bytes - HB_BONE;
+                    mma_chunk<4, 4, HB_BONE, PS>(ws, buf, fh[0], fl[0], &c1[ACC_BLK * blk], &c2[ACC_BLK * blk], lane);
+                });
 #pragma unroll 1
                 for (int b = 1; b < N_BONES; ++b) {
-                    if constexpr (HN_FAR_HOLD_A) {
-                        resident_held();
-                        mma_held<4, 4, PS>(ws, held, fh[0], fl[0], &c1[0], &c2[0]);
-                        resident_held();
-                        mma_held<4, 4, PS>(ws, held, fh[0], fl[0], &c1[HN_EXP_ACC], &c2[HN_EXP_ACC]);
-                    } else {
-                        buf = resident(buf);
-                        mma_chunk<4, 4, 0, PS>(ws, buf, fh[0], fl[0], &c1[0], &c2[0], lane);
-                        buf = resident(buf);
-                        mma_chunk<4, 4, 0, PS>(ws, buf, fh[0], fl[0], &c1[HN_EXP_ACC], &c2[HN_EXP_ACC], lane);
-                    }
+                    ws.held();
+                    mma_held<4, 4, PS>(ws, held, fh[0], fl[0], &c1[0], &c2[0]);
+                    ws.held();
+                    mma_held<4, 4, PS>(ws, held, fh[0], fl[0], &c1[ACC_BLK], &c2[ACC_BLK]);
                 }
             } else {
             load_bone(0, fh[0], fl[0]);
@@ -1202,27 +1089,28 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 fin(std::integral_constant<int, ti>{}, st, nd);
             });
         };
-        // the same under the shared epilogue: the phase type gets the tile's index
-        [[maybe_unused]] auto block_epilogue_far = [&](auto NT_, auto& c1, auto& c2, auto&& ph, auto&& fin) {
-            constexpr int NTT = decltype(NT_)::value;
-            static_for<NTT>([&](auto TI) {
-                constexpr int ti = decltype(TI)::value;
-                EpiState st;
-                arm(st);
-                st.c1 = c1[ti];
-                st.c2 = c2[ti];
-                const FarTile ft{ti};
-                Epi<true, std::remove_reference_t<decltype(ph)>, FarTile> epi{st, ph, ft};
-                epi.run_all();
-                split_finish<true>(st);
-                fin(std::integral_constant<int, ti>{}, st, ft);
-            });
-        };
-        [[maybe_unused]] auto far_pre = [](auto T, const char*) { return FarTile{decltype(T)::value}; };
         using I2 = std::integral_constant<int, 2>;
         using I8t = std::integral_constant<int, 8>;
         using BTrue = std::integral_constant<bool, true>;
         using BFalse = std::integral_constant<bool, false>;
+        // The SDF network's softplus layers by program instance: the lean all-far program computes the epilogue once per lane row and
+        // keeps no a_l (its reverse sweep is discarded); the others compute it per lane and keep a_{slot + 1} for the sweep.
+        auto sp_phase = [&]() {
+            if constexpr (LEAN)
+                return PhFarShared<false>{shf.img};
+            else
+                return PhSoftplus{};
+        };
+        auto sp_fin = [&](h8(&oh)[16], h8(&ol)[16], int slot) {
+            if constexpr (LEAN)
+                return to_regs(oh, ol);
+            else
+                return to_regs_keep(KeepFull{}, oh, ol, HS_A1 + slot);
+        };
+        // a hidden layer (one chunk per output tile, the bias in its tail): in -> out
+        auto hidden = [&](h8(&ih)[16], h8(&il)[16], h8(&oh)[16], h8(&ol)[16], int slot) __attribute__((always_inline)) {
+            run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ih, il, lane, h, no_pre, sp_phase(), sp_fin(oh, ol, slot), no_store);
+        };
 
         float g[3] = {0.f, 0.f, 0.f}, rgb[3] = {0.f, 0.f, 0.f}, rgb1[3] = {0.f, 0.f, 0.f};
         float sdf = 0.f;
@@ -1242,41 +1130,14 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 c2[ti] = zero16();
             }
             feature_pass(I2{}, BTrue{}, c1, c2, std::integral_constant<int, HB_LEFT_T>{}, std::integral_constant<int, HB_HID>{}, IPF{});
-            if constexpr (SH)
-                block_epilogue_far(I8t{}, c1, c2, PhFarShared<0, far_dst(HS_A1 + 0), 0>{shf.img}, to_regs(ah, al));
-            else
-                block_epilogue(I8t{}, c1, c2, PhSp{}, to_regs_keep(ah, al, HS_A1 + 0));
+            block_epilogue(I8t{}, c1, c2, sp_phase(), sp_fin(ah, al, 0));
         }
-        if constexpr (SH) {
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, far_dst(HS_A1 + 1), 0>{shf.img}, to_regs(bh, bl), no_store);   // lin1
-        } else {
-#if HN_DEFER_STASH
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 1));   // lin1
-#else
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_keep(bh, bl, HS_A1 + 1), no_store);   // lin1
-#endif
-        }
-        if constexpr (SH) {
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<0, far_dst(HS_A1 + 2), 0>{shf.img}, to_regs(ah, al), no_store);   // lin2
-        } else {
-#if HN_DEFER_STASH
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSp{}, to_regs_hold(ah, al), store_tile(HS_A1 + 2));   // lin2
-#else
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSp{}, to_regs_keep(ah, al, HS_A1 + 2), no_store);   // lin2
-#endif
-        }
+        hidden(ah, al, bh, bl, 1);   // lin1
+        hidden(bh, bl, ah, al, 2);   // lin2
         // lin3 -> a4, in bh / bl like every layer's output: lin4's hidden part reads them from there.  (They used to go
         // through the stash -- 32 KB written and read back at once per tile, an HBM round trip of ~10 000 cycles in front
         // of lin4 in the in-kernel stamps.)
-        if constexpr (SH) {
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, far_dst(HS_A1 + 3), 0>{shf.img}, to_regs(bh, bl), no_store);   // lin3
-        } else {
-#if HN_DEFER_STASH
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 3));   // lin3
-#else
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_keep(bh, bl, HS_A1 + 3), no_store);   // lin3
-#endif
-        }
+        hidden(ah, al, bh, bl, 3);   // lin3
         if ((HN_DBG(a) >> 8) == 3) return true;   // phase timing aid
         // ---- lin4 = [a4 | features] / sqrt2 -> a5: 8 hidden tiles (bias from the tail), then the feature pass
         {
@@ -1291,52 +1152,27 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 mma_tile<16, 0, nbytes, PH>(ws, buf, bh, bl, c1[ti], c2[ti], lane);
             });
             feature_pass(I2{}, BFalse{}, c1, c2, std::integral_constant<int, HB_LEFT>{}, std::integral_constant<int, HB_HID>{}, IPF{});
-            if constexpr (SH)
-                block_epilogue_far(I8t{}, c1, c2, PhFarShared<0, far_dst(HS_A1 + 4), 0>{shf.img}, to_regs(ah, al));
-            else
-                block_epilogue(I8t{}, c1, c2, PhSp{}, to_regs_keep(ah, al, HS_A1 + 4));
+            block_epilogue(I8t{}, c1, c2, sp_phase(), sp_fin(ah, al, 4));
         }
-        if constexpr (SH) {
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<0, far_dst(HS_A1 + 5), 0>{shf.img}, to_regs(bh, bl), no_store);   // lin5
-        } else {
-#if HN_DEFER_STASH
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_hold(bh, bl), store_tile(HS_A1 + 5));   // lin5
-#else
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ah, al, lane, h, no_pre, PhSp{}, to_regs_keep(bh, bl, HS_A1 + 5), no_store);   // lin5
-#endif
-        }
-        if constexpr (SH) {
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<0, far_dst(HS_A1 + 6), 0>{shf.img}, to_regs(ah, al), no_store);   // lin6
-        } else {
-#if HN_DEFER_STASH
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSp{}, to_regs_hold(ah, al), store_tile(HS_A1 + 6));   // lin6
-#else
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, bh, bl, lane, h, no_pre, PhSp{}, to_regs_keep(ah, al, HS_A1 + 6), no_store);   // lin6
-#endif
-        }
+        hidden(ah, al, bh, bl, 5);   // lin5
+        hidden(bh, bl, ah, al, 6);   // lin6
         // ---- lin7 -> a8; sdf = W8[0,:] a8 + b8; seed of the reverse sweep dz7 = sigma'(z7) W8[0,:] (scaled)
         float sdf_acc = 0.f, sdf_acc1 = 0.f;   // (16x16x32: the lane's registers of column block 0 / 1 are two samples)
         auto lin7 = [&](auto NA_) {   // NA_: the size of the chunk that follows the layer, a constant
         // (the shared epilogue leaves a8's tile in the line FAR_Z: every lane needs its 16 values for the sdf row and the seed)
         run_layer_c<8, 16, 1, true, true, HB_HID, decltype(NA_)::value, P7>(
             ws, ah, al, lane, h,
-            [&](auto T, const char* tail) {
-                (void)T;
-                if constexpr (SH)
-                    return FarActT{tail_tile(tail, 1, h), decltype(T)::value};
-                else
-                    return Act{tail_tile(tail, 1, h)};
-            },
+            [&](auto, const char* tail) { return Act{tail_tile(tail, 1, h)}; },
             [&]() {
-                if constexpr (SH)
-                    return PhFarShared<0, DST_LINE, 0>{shf.img};
+                if constexpr (LEAN)
+                    return PhFarShared<true>{shf.img};
                 else
-                    return PhSp{};
+                    return PhSoftplus{};
             }(),
             [&](auto T, EpiState& st, const auto& w8) {
                 constexpr int t = decltype(T)::value;
                 asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
-                if constexpr (SH) shf.line_load(st.v);
+                if constexpr (LEAN) shf.line_load(st.v);
                 f32x16 dz;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
@@ -1344,14 +1180,14 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                         sdf_acc1 = fmaf(w8.v[i], st.v[i], sdf_acc1);
                     else
                         sdf_acc = fmaf(w8.v[i], st.v[i], sdf_acc);
-                    if constexpr (!RH) dz[i] = dsoftplus_from_act(st.v[i]) * w8.v[i] * BWD_SCALE;
+                    if constexpr (!LEAN) dz[i] = dsoftplus_from_act(st.v[i]) * w8.v[i] * BWD_SCALE;
                 }
                 if (FULL) {
                     bh[2 * t] = st.hi[0];   // a8 feeds lin8
                     bl[2 * t] = st.lo[0];
                     bh[2 * t + 1] = st.hi[1];
                     bl[2 * t + 1] = st.lo[1];
-                    if constexpr (!RH) {   // (the seed of a sweep that is discarded is not formed)
+                    if constexpr (!LEAN) {   // (the seed of a sweep that is discarded is not formed)
                     Frags f;
                     split_tile(dz, f.hi[0], f.lo[0], f.hi[1], f.lo[1]);
                     stash_frags(HS_DZ7)(T, f);
@@ -1406,44 +1242,16 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         if ((HN_DBG(a) >> 8) == 6) return true;   // phase timing aid
         // ---- reverse sweep: dz_{l-1} = sigma'(z_{l-1}) * (W_l^T dz_l); sigma' from the stashed activation a_l
         auto act_of = [&](int act_slot) {
-#if defined(HN_STASH_HALF) && HN_STASH_HALF
-            return [&sh, act_slot](auto T, const char*) {
-                if constexpr (MODE == 1)
-                    return Act{sh.tile_load_half(act_slot, decltype(T)::value)};
-                else
-                    return Act{sh.tile_load(act_slot, decltype(T)::value)};
-            };
-#else
-            return [&sh, act_slot](auto T, const char*) {
-                (void)sh;
-                (void)act_slot;
-                if constexpr (RAW)
-                    return NoData{};
-                else
-                    return Act{sh.tile_load(act_slot, decltype(T)::value)};
-            };
-#endif
+            return [&sh, act_slot](auto T, const char*) { return Act{sh.tile_load(act_slot, decltype(T)::value)}; };
         };
-        if constexpr (!RH) {
+        // W_{l+1}^T: dz_{l+1} (in) -> dz_l (out); adjoint mode: every dz_l also goes to the stash as an fp32 tile, slot HS_DZ + l
+        auto reverse = [&](h8(&ih)[16], h8(&il)[16], h8(&oh)[16], h8(&ol)[16], int l) __attribute__((always_inline)) {
+            run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ih, il, lane, h, act_of(HS_A1 + l), PhDsig{}, to_regs_keep(KeepAdj{}, oh, ol, HS_DZ + l), no_store);
+        };
+        if constexpr (!LEAN) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) sh.frag_load(HS_DZ7 * SLOT_BYTES, s, ah[s], al[s]);
         }
-        // (adjoint mode: every dz_l also goes to the stash as an fp32 tile, slot HS_DZ + l)
-        auto to_regs_t = [&](h8(&oh)[16], h8(&ol)[16], int tile_slot) {
-            return [&oh, &ol, tile_slot, &sh, &park](auto T, EpiState& st, const auto&) {
-                constexpr int t = decltype(T)::value;
-                asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
-                oh[2 * t] = st.hi[0];
-                ol[2 * t] = st.lo[0];
-                oh[2 * t + 1] = st.hi[1];
-                ol[2 * t + 1] = st.lo[1];
-                park(oh[2 * t], ol[2 * t], oh[2 * t + 1], ol[2 * t + 1]);
-                (void)tile_slot;
-                (void)sh;
-                if constexpr (ADJ) sh.tile_store(tile_slot, t, st.vec());
-                return NoData{};
-            };
-        };
         // the zero fragments of the all-far program's discarded passes: two run-time zeros, hi and lo (with one, the first MFMAs of a
         // group's two accumulators are one expression)
         [[maybe_unused]] h8 zh[16], zl[16];
@@ -1460,25 +1268,17 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 zl[s] = z2;
             }
         };
-        if constexpr (RH) {
-            // The all-far program whose Jacobian pass multiplies zero fragments (HN_FAR_JAC_ZERO): d sdf / d p is a run-time +0 by
-            // construction, nothing reads dz6 .. dz0, and the sweep's 56 products (FAR_REV_TABLE) are discarded like that pass's.
-            //   entry    the sweep's first chunk (W7^T, tile 0) is in flight to buffer X, begun by lin8; ws.phase = Y
-            //   group 0  acquire: X landed.  The second chunk -> Y, its pieces in this group's slots.  MFMAs read X.
-            //   group 1  acquire: Y landed, every wave has read X for the last time -- so the JACOBIAN PASS's FIRST CHUNK, the next chunk
-            //            that is needed, goes to X here, at its own offset (56 chunks on from the sweep's first) and at the size the
-            //            full stream fetches it with, and has the whole sweep to land.  k-step 0 of Y goes into registers; MFMAs read Y.
-            //   groups 2 .. 55  read nothing (HN_FAR_HOLD_A; without it they read Y, resident).  The next fetch into Y is the Jacobian
-            //            pass's second chunk, issued behind that pass's first acquire, whose barrier every wave reaches after group 55.
-            //   exit     ws.goff = 57 chunks on from the sweep's first, ws.phase = Y, the Jacobian pass's first chunk in X: the full
-            //            stream's state behind W1^T, so the pass below is untouched.
+        if constexpr (LEAN) {
+            // The all-far program whose Jacobian pass multiplies zero fragments: d sdf / d p is a run-time +0 by construction, nothing
+            // reads dz6 .. dz0, and the sweep's 56 products (FAR_REV_TABLE) are discarded like that pass's.
+            // discarded_pass: 56 groups; its first chunk (W7^T, tile 0) was begun by lin8, the chunk needed next is the JACOBIAN PASS's
+            // FIRST CHUNK, 56 chunks on from the sweep's first, and the pass below is untouched.
             // Every group is one tile of the full sweep -- 16 k-steps onto zeroed accumulators, PH MFMAs per product -- with the zero
             // fragment as B (two run-time zeros, hi and lo, as in the other passes) and its results sunk: no epilogue, no sigma' from a
-            // stashed a_l, no fragments of dz parked or stashed.  A reverse chunk is packed finite fp16 from end to end (the static_assert at
-            // FAR_STREAM_SKIPPED), so the held k-step is finite whichever layer's it is.  mma_held launders its A fragment per group:
-            // the disassembly keeps the sweep's 56 x 16 PH MFMAs (tests/test_far_hold_isa.py).
+            // stashed a_l, no fragments of dz parked or stashed.  A reverse chunk has no tail, so the held k-step is finite whichever
+            // layer's it is.  mma_held launders its A fragment per group: the disassembly keeps the sweep's 56 x 16 PH MFMAs
+            // (tests/test_far_hold_isa.py).
             far_zeros();   // (the Jacobian pass below multiplies the same two)
-            const int rfirst = ws.goff - HB_BWD;   // stream offset of the sweep's first chunk (in flight)
             f32x16 r1, r2;
             // the results of MFMAs that run for the dense count.  A single-pass product never touches its second accumulator, which is
             // then not sunk: its 16 registers of zeros per group cost k_field2_hand_f16<1> 22 more spilled registers, twelve of them
@@ -1489,43 +1289,23 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 else
                     asm volatile("" ::"v"(c1));
             };
-            const char* buf = ws.template acquire<0>();
-            ws.template begin_c<HB_BWD>();
-            r1 = zero16();
-            r2 = zero16();
-            mma_tile<16, 0, HB_BWD, PH>(ws, buf, zh, zl, r1, r2, lane);
-            sink(r1, r2);
-            buf = ws.template acquire<0>();
-            [[maybe_unused]] HeldA held;
-            if constexpr (HN_FAR_HOLD_A) held = held_load(buf);
-            ws.template begin_at_c<HB_BWD>(rfirst + FAR_REV_TABLE * HB_BWD);
-            r1 = zero16();
-            r2 = zero16();
-            mma_tile<16, 0, HB_BWD, PH>(ws, buf, zh, zl, r1, r2, lane);
-            sink(r1, r2);
+            HeldA held = discarded_pass(std::integral_constant<int, HB_BWD>{}, std::integral_constant<int, FAR_REV_TABLE>{}, [&](auto, const char* buf) {
+                r1 = zero16();
+                r2 = zero16();
+                mma_tile<16, 0, HB_BWD, PH>(ws, buf, zh, zl, r1, r2, lane);
+                sink(r1, r2);
+            });
             static_for<FAR_REV_TABLE - FAR_TABLE_FETCHED>([&](auto) {
                 r1 = zero16();
                 r2 = zero16();
-                if constexpr (HN_FAR_HOLD_A) {
-                    resident_held();
-                    mma_held<1, 16, PH>(ws, held, zh, zl, &r1, &r2);
-                } else {
-                    buf = resident(buf);
-                    mma_tile<16, 0, 0, PH>(ws, buf, zh, zl, r1, r2, lane);
-                }
+                ws.held();
+                mma_held<1, 16, PH>(ws, held, zh, zl, &r1, &r2);
                 sink(r1, r2);
             });
         } else {
-        if constexpr (SH)
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 6>{shf.img}, to_regs_t(bh, bl, HS_DZ + 6), no_store);   // W7^T -> dz6
-        else
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 6), PhDs{}, to_regs_t(bh, bl, HS_DZ + 6), no_store);   // W7^T -> dz6
-        if constexpr (SH)
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 5>{shf.img}, to_regs_t(ah, al, HS_DZ + 5), no_store);   // W6^T -> dz5
-        else
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, act_of(HS_A1 + 5), PhDs{}, to_regs_t(ah, al, HS_DZ + 5), no_store);   // W6^T -> dz5
-        auto dz4_layer = [&](auto&& pre4, auto&& ph4) {
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, pre4, ph4,                               // W5^T -> dz4 (kept)
+        reverse(ah, al, bh, bl, 6);   // W7^T -> dz6
+        reverse(bh, bl, ah, al, 5);   // W6^T -> dz5
+        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 4), PhDsig{},                               // W5^T -> dz4 (kept)
                                          [&](auto T, EpiState& st, const auto&) {
                                              constexpr int t = decltype(T)::value;
                                              asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
@@ -1538,27 +1318,10 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                                              return NoData{};
                                          },
                                          no_store);
-        };
-        if constexpr (SH)
-            dz4_layer(far_pre, PhFarShared<1, DST_NONE, HS_A1 + 4>{shf.img});
-        else
-            dz4_layer(act_of(HS_A1 + 4), PhDs{});
-        if constexpr (SH)
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 3>{shf.img}, to_regs_t(ah, al, HS_DZ + 3), no_store);   // W4h^T -> dz3
-        else
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, act_of(HS_A1 + 3), PhDs{}, to_regs_t(ah, al, HS_DZ + 3), no_store);   // W4h^T -> dz3
-        if constexpr (SH)
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 2>{shf.img}, to_regs_t(bh, bl, HS_DZ + 2), no_store);   // W3^T -> dz2
-        else
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 2), PhDs{}, to_regs_t(bh, bl, HS_DZ + 2), no_store);   // W3^T -> dz2
-        if constexpr (SH)
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 1>{shf.img}, to_regs_t(ah, al, HS_DZ + 1), no_store);   // W2^T -> dz1
-        else
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, bh, bl, lane, h, act_of(HS_A1 + 1), PhDs{}, to_regs_t(ah, al, HS_DZ + 1), no_store);   // W2^T -> dz1
-        if constexpr (SH)
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, far_pre, PhFarShared<1, DST_NONE, HS_A1 + 0>{shf.img}, to_regs_t(bh, bl, HS_DZ + 0), no_store);   // W1^T -> dz0
-        else
-        run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 0), PhDs{}, to_regs_t(bh, bl, HS_DZ + 0), no_store);   // W1^T -> dz0
+        reverse(bh, bl, ah, al, 3);   // W4h^T -> dz3
+        reverse(ah, al, bh, bl, 2);   // W3^T -> dz2
+        reverse(bh, bl, ah, al, 1);   // W2^T -> dz1
+        reverse(ah, al, bh, bl, 0);   // W1^T -> dz0
         }   // the real sweep
 
         if ((HN_DBG(a) >> 8) == 7) return true;   // phase timing aid
@@ -1566,90 +1329,53 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         //      bh/bl), then W4[:, 256:]^T dz4 (reloaded into ah/al)
         // G = W0^T dz0 + W4[:, 256:]^T dz4 accumulated per tile (chunks alternate between the two matrices),
         // so that the features and the Jacobian are visited once
-        // (the all-far program without table chunks discards the pass's products and multiplies the zero fragment instead, HN_FAR_JAC_ZERO
-        //  below: dz0 and dz4 are dead behind the reverse sweep, and nothing is reloaded or moved here)
-        constexpr bool JZ = FS && HN_FAR_JAC_ZERO;
-        if constexpr (!JZ) {
+        // (the all-far program without table chunks discards the pass's products and multiplies the zero fragment instead: dz0 and dz4
+        //  are dead behind the reverse sweep, and nothing is reloaded or moved here)
+        if constexpr (!LEAN) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) sh.frag_load(HS_DZ4 * SLOT_BYTES, s, ah[s], al[s]);
         // dz0 (parked in AGPRs by the last reverse layer) is the B operand of 44 chunks: back into VGPRs once, here
-#if HN_JAC_VARIANT == 0
-#pragma unroll
-        for (int s = 0; s < 16; ++s) asm volatile("" : "+v"(bh[s]), "+v"(bl[s]));
-#elif HN_JAC_VARIANT == 2
 #pragma unroll
         for (int s = 0; s < 16; ++s) asm volatile("" : "+a"(bh[s]), "+a"(bl[s]), "+a"(ah[s]), "+a"(al[s]));
-#elif HN_JAC_VARIANT == 3
-#pragma unroll
-        for (int s = 0; s < 16; ++s) asm volatile("" : "+v"(bh[s]), "+v"(bl[s]), "+a"(ah[s]), "+a"(al[s]));
-#endif
         }
-        if constexpr (FS) {
+        if constexpr (LEAN) {
             // The all-far program that fetches no table chunk (FAR_JAC_TABLE): the pass's 88 products are discarded, so all but its
             // first two chunks are neither fetched nor waited for.
-            //   entry    the pass's first chunk (the leftover block's W0 tile) is in flight to buffer X, begun by the last reverse
-            //            layer; ws.phase = Y
-            //   group 0  acquire: X landed.  The second chunk -> Y, its pieces in this group's slots.  MFMAs read X.
-            //   group 1  acquire: Y landed, every wave has read X for the last time -- so COLOUR LIN0's FIRST CHUNK, the next chunk
-            //            that is needed, goes to X here, at its own offset (88 chunks on from the pass's first) and at the size the
-            //            full stream fetches it with, and has the whole pass to land.  MFMAs read Y, resident from here on.
-            //   groups 2 .. 87  read Y.  The next fetch into Y is colour lin0's second chunk, issued behind that layer's first
-            //            acquire, whose barrier every wave reaches after group 87.
-            //   exit     ws.goff = 89 chunks on from the pass's first, ws.phase = Y, colour lin0's first chunk in X: the full stream's.
-            // Groups, B operands (dz0 and dz4 in turn), accumulators and the sinks of the results are the full stream's.
-            // HN_FAR_JAC_ZERO: ... except the B operands, which are the zero fragment in every group: the last products of the tile that
-            // still switched the matrix pipe on sample-dependent values for nothing.  Two run-time zeros, hi and lo, as in the feature
+            // discarded_pass: 88 groups; its first chunk is the leftover block's W0 tile, the chunk needed next is COLOUR LIN0's FIRST
+            // CHUNK, 88 chunks on from the pass's first.
+            // Groups (a tile's "dz0" group, then its "dz4" group), accumulators and the sinks of the results are the full stream's.
+            // The B operands are the zero fragment in every group: with dz0 and dz4 they were the last products of the tile that still
+            // switched the matrix pipe on sample-dependent values for nothing.  Two run-time zeros, hi and lo, as in the feature
             // passes (with one, the first MFMAs of a group's two accumulators are one expression).
-            // HN_FAR_HOLD_A: groups 2 .. 87 read nothing.  Their A operand is k-step 0 of Y, in registers from the acquire that made Y
-            // resident to the end of the pass -- every byte of a table chunk is a packed finite fp16 value (the static_assert at
-            // FAR_STREAM_SKIPPED), and no result of the pass is kept.  Every iteration of the bone loop is then the same expression
-            // on the same operands: mma_held launders its A fragment per group, and the disassembly keeps 88 x 48 MFMAs
-            // (tests/test_far_hold_isa.py).
-            if constexpr (JZ && !RH) far_zeros();
-            auto pick = [](auto& zero, auto& real) -> auto& {
-                if constexpr (JZ)
-                    return zero;
-                else
-                    return real;
-            };
-            const auto &b0h = pick(zh, bh), &b0l = pick(zl, bl), &b4h = pick(zh, ah), &b4l = pick(zl, al);   // "dz0", "dz4"
-            const int jfirst = ws.goff - HB_BWD;   // stream offset of the pass's first chunk (in flight)
-            const char* buf = ws.template acquire<0>();
-            ws.template begin_c<HB_BWD>();
-            [[maybe_unused]] HeldA held;
-            // a tile on the resident chunk: its "dz0" group, then its "dz4" group
-            auto resident_tile = [&](f32x16& g1, f32x16& g2) {
+            // No result of the pass is kept.  Every iteration of the bone loop is the same expression on the same operands: mma_held
+            // launders its A fragment per group, and the disassembly keeps 88 x 48 MFMAs (tests/test_far_hold_isa.py).
+            HeldA held;
+            // a tile on the held k-step: its "dz0" group, then its "dz4" group
+            auto held_tile = [&](f32x16& g1, f32x16& g2) {
                 g1 = zero16();
                 g2 = zero16();
-                if constexpr (HN_FAR_HOLD_A) {
-                    resident_held();
-                    mma_held<1, 16, PJ>(ws, held, b0h, b0l, &g1, &g2);
-                    resident_held();
-                    mma_held<1, 16, PJ>(ws, held, b4h, b4l, &g1, &g2);
-                } else {
-                    buf = resident(buf);
-                    mma_tile<16, 0, 0, PJ>(ws, buf, b0h, b0l, g1, g2, lane);
-                    buf = resident(buf);
-                    mma_tile<16, 0, 0, PJ>(ws, buf, b4h, b4l, g1, g2, lane);
-                }
+                ws.held();
+                mma_held<1, 16, PJ>(ws, held, zh, zl, &g1, &g2);
+                ws.held();
+                mma_held<1, 16, PJ>(ws, held, zh, zl, &g1, &g2);
             };
             {
                 f32x16 L1[2], L2[2];
-                L1[0] = zero16();
-                L2[0] = zero16();
-                mma_tile<16, 0, HB_BWD, PJ>(ws, buf, b0h, b0l, L1[0], L2[0], lane);
-                buf = ws.template acquire<0>();
-                if constexpr (HN_FAR_HOLD_A) held = held_load(buf);
-                ws.template begin_at_c<HB_BWD>(jfirst + FAR_JAC_TABLE * HB_BWD);
-                mma_tile<16, 0, HB_BWD, PJ>(ws, buf, b4h, b4l, L1[0], L2[0], lane);
-                resident_tile(L1[1], L2[1]);
+                held = discarded_pass(std::integral_constant<int, HB_BWD>{}, std::integral_constant<int, FAR_JAC_TABLE>{}, [&](auto G, const char* buf) {
+                    if constexpr (decltype(G)::value == 0) {
+                        L1[0] = zero16();
+                        L2[0] = zero16();
+                    }
+                    mma_tile<16, 0, HB_BWD, PJ>(ws, buf, zh, zl, L1[0], L2[0], lane);   // the first tile's "dz0" group, then its "dz4" group
+                });
+                held_tile(L1[1], L2[1]);
                 asm volatile("" ::"v"(L1[0]), "v"(L2[0]), "v"(L1[1]), "v"(L2[1]));   // (the results of MFMAs that run for the dense count)
             }
 #pragma unroll 1
             for (int b = 0; b < N_BONES; ++b) {
                 f32x16 G1[2], G2[2];
-                resident_tile(G1[0], G2[0]);
-                resident_tile(G1[1], G2[1]);
+                held_tile(G1[0], G2[0]);
+                held_tile(G1[1], G2[1]);
                 asm volatile("" ::"v"(G1[0]), "v"(G2[0]), "v"(G1[1]), "v"(G2[1]));
             }
         } else {
@@ -1828,10 +1554,10 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     for (int i = 0; i < 16; ++i) c1[4 * blk + ti][i] += bias[i];
                 });
             });
-            block_epilogue(I8t{}, c1, c2, PhRelu{}, to_regs_t(bh, bl, HS_C + 0));
+            block_epilogue(I8t{}, c1, c2, PhRelu{}, to_regs_keep(KeepAdj{}, bh, bl, HS_C + 0));
         }
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PC>(ws, bh, bl, lane, h, no_pre, PhRelu{}, to_regs_t(ah, al, HS_C + 1), no_store);   // colour lin1
-        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PC>(ws, ah, al, lane, h, no_pre, PhRelu{}, to_regs_t(bh, bl, HS_C + 2), no_store);   // colour lin2
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PC>(ws, bh, bl, lane, h, no_pre, PhRelu{}, to_regs_keep(KeepAdj{}, ah, al, HS_C + 1), no_store);   // colour lin1
+        run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PC>(ws, ah, al, lane, h, no_pre, PhRelu{}, to_regs_keep(KeepAdj{}, bh, bl, HS_C + 2), no_store);   // colour lin2
         struct W3 {
             f32x16 w[3];
         };
@@ -1890,12 +1616,10 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         }
         return false;
         };   // program
-        if constexpr (FAR_ARM && !HN_DBG_FAR_NO_EPILOGUE) {
+        if constexpr (FAR_ARM) {
             const bool out = !far ? program(std::integral_constant<int, 0>{})
                                   : ((a.far_epilogue != 0 && a.far_stream != 0) ? program(std::integral_constant<int, 2>{}) : program(std::integral_constant<int, 1>{}));
             if (out) return;
-        } else if constexpr (FAR_ARM) {
-            if (far ? program(std::integral_constant<int, 1>{}) : program(std::integral_constant<int, 0>{})) return;
         } else {
             if (program(std::integral_constant<int, 0>{})) return;
         }

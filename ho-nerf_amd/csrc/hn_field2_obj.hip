@@ -11,9 +11,6 @@
 
 #include "hn_field_launch.h"
 #include "hn_mlp2.h"
-#ifndef HN_PARK_AGPR
-#define HN_PARK_AGPR 1
-#endif
 
 namespace hn {
 namespace v2 {
@@ -154,9 +151,7 @@ __device__ __forceinline__ void obj_adjoint(const Obj2Args& a, WStream& ws, Stas
             ol[2 * t] = st.lo[0];
             oh[2 * t + 1] = st.hi[1];
             ol[2 * t + 1] = st.lo[1];
-#if HN_PARK_AGPR
             asm volatile("" : "+a"(oh[2 * t]), "+a"(ol[2 * t]), "+a"(oh[2 * t + 1]), "+a"(ol[2 * t + 1]));
-#endif
             return NoData{};
         };
     };
@@ -169,9 +164,7 @@ __device__ __forceinline__ void obj_adjoint(const Obj2Args& a, WStream& ws, Stas
             ol[2 * t] = st.lo[0];
             oh[2 * t + 1] = st.hi[1];
             ol[2 * t + 1] = st.lo[1];
-#if HN_PARK_AGPR
             asm volatile("" : "+a"(oh[2 * t]), "+a"(ol[2 * t]), "+a"(oh[2 * t + 1]), "+a"(ol[2 * t + 1]));
-#endif
             if constexpr (PG) {
                 sig(arr, t, st.vec(), sig_scale);
                 if (arr_pre >= 0) sig(arr_pre, t, pd.v, 1.f);
@@ -309,9 +302,7 @@ __device__ __forceinline__ void obj_adjoint(const Obj2Args& a, WStream& ws, Stas
             ol[2 * t] = st.lo[0];
             oh[2 * t + 1] = st.hi[1];
             ol[2 * t + 1] = st.lo[1];
-#if HN_PARK_AGPR
             asm volatile("" : "+a"(oh[2 * t]), "+a"(ol[2 * t]), "+a"(oh[2 * t + 1]), "+a"(ol[2 * t + 1]));
-#endif
             sh.tile_store(w_slot, t, st.wvec());
             return NoData{};
         };
@@ -651,9 +642,7 @@ __device__ __forceinline__ void field2_obj_body(const Obj2Args& a) {
                 ol[2 * t] = st.lo[0];
                 oh[2 * t + 1] = st.hi[1];
                 ol[2 * t + 1] = st.lo[1];
-#if HN_PARK_AGPR
                 asm volatile("" : "+a"(oh[2 * t]), "+a"(ol[2 * t]), "+a"(oh[2 * t + 1]), "+a"(ol[2 * t + 1]));   // as hn_field2_hand.hip: park
-#endif
                 return NoData{};
             };
         };
@@ -670,17 +659,13 @@ __device__ __forceinline__ void field2_obj_body(const Obj2Args& a) {
                 ol[2 * t] = st.lo[0];
                 oh[2 * t + 1] = st.hi[1];
                 ol[2 * t + 1] = st.lo[1];
-#if HN_PARK_AGPR
                 asm volatile("" : "+a"(oh[2 * t]), "+a"(ol[2 * t]), "+a"(oh[2 * t + 1]), "+a"(ol[2 * t + 1]));   // as hn_field2_hand.hip: park
-#endif
                 } else {
                     (void)ol;
                     asm volatile("" : "+v"(st.hi[0]), "+v"(st.hi[1]));
                     oh[2 * t] = st.hi[0];
                     oh[2 * t + 1] = st.hi[1];
-#if HN_PARK_AGPR
                     asm volatile("" : "+a"(oh[2 * t]), "+a"(oh[2 * t + 1]));
-#endif
                 }
                 if (FULL && !(HN_DBG(a) & 1)) sh.tile_store(stash_slot, t, st.vec());
                 return NoData{};
@@ -837,17 +822,13 @@ __device__ __forceinline__ void field2_obj_body(const Obj2Args& a) {
                 ol[2 * t] = st.lo[0];
                 oh[2 * t + 1] = st.hi[1];
                 ol[2 * t + 1] = st.lo[1];
-#if HN_PARK_AGPR
                 asm volatile("" : "+a"(oh[2 * t]), "+a"(ol[2 * t]), "+a"(oh[2 * t + 1]), "+a"(ol[2 * t + 1]));
-#endif
                 } else {
                     (void)ol;
                     asm volatile("" : "+v"(st.hi[0]), "+v"(st.hi[1]));
                     oh[2 * t] = st.hi[0];
                     oh[2 * t + 1] = st.hi[1];
-#if HN_PARK_AGPR
                     asm volatile("" : "+a"(oh[2 * t]), "+a"(oh[2 * t + 1]));
-#endif
                 }
                 if constexpr (ADJ) sh.tile_store(dz_slot, t, st.vec());
                 return NoData{};
@@ -1024,9 +1005,7 @@ __device__ __forceinline__ void field2_obj_body(const Obj2Args& a) {
                 ol[2 * t] = st.lo[0];
                 oh[2 * t + 1] = st.hi[1];
                 ol[2 * t + 1] = st.lo[1];
-#if HN_PARK_AGPR
                 asm volatile("" : "+a"(oh[2 * t]), "+a"(ol[2 * t]), "+a"(oh[2 * t + 1]), "+a"(ol[2 * t + 1]));
-#endif
                 if constexpr (ADJ) sh.tile_store(c_slot, t, st.vec());
                 return NoData{};
             };

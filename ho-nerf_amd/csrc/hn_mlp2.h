@@ -298,22 +298,10 @@ struct WStream {
         stamp(3);
         return lds + (phase ^ 1) * CHUNK_MAX;
     }
-    // A RESIDENT chunk (the all-far hand program's passes over the feature space, hn_field2_hand.hip): the buffer that the last
-    // acquire() returned is read again by the next group of MFMAs, nothing having been fetched for that group.  No wait and no
-    // barrier -- nothing lands, and the rule a fetch has to keep is unchanged: it goes into buffer X only behind a barrier that every
-    // wave reaches after its last read of X, so while a chunk is resident the fetches in flight go to the OTHER buffer and the next
-    // acquire() is the barrier that frees this one.  What remains is the compiler's side of acquire(): the memory clobber, so that the
-    // group's ds_read_b128 are issued again and no A fragment of an earlier group is kept in registers or hoisted out of a loop.  The
-    // stamps keep the per-chunk record of the timing builds in step.
-    __device__ __forceinline__ const char* hold(const char* buf) {
-        stamp(1);
-        stamp(2);
-        asm volatile("" ::: "memory");
-        stamp(3);
-        return buf;
-    }
-    // ... and a group that reads NOTHING: its A fragments are held in registers (mma_held below).  No clobber either; the stamps alone,
-    // so that a timing build still records one chunk start per group.
+    // A group of MFMAs that reads NOTHING (the all-far hand program's discarded passes, hn_field2_hand.hip): its A fragments are held
+    // in registers (mma_held below).  No wait, no barrier and no memory clobber -- nothing lands and nothing is read.  The rule a
+    // fetch has to keep is unchanged: it goes into buffer X only behind a barrier that every wave reaches after its last read of X.
+    // The stamps alone, so that a timing build still records one chunk start per group.
     __device__ __forceinline__ void held() {
         stamp(1);
         stamp(2);
@@ -668,7 +656,7 @@ __device__ __forceinline__ void mma_chunk(WStream& ws, const char* buf, const h8
 
 // The same group of NT tiles x KS k-steps -- the same 3 NT KS MFMAs in the same order onto the same accumulators -- with ONE k-step's
 // A fragments, [hi | lo] in 8 VGPRs, HELD in registers for every block of the group: no LDS read, no DMA piece.  For groups whose
-// products are +-0 or discarded whatever finite A they multiply (the resident groups of the all-far hand program).
+// products are +-0 or discarded whatever finite A they multiply (the discarded passes of the all-far hand program).
 // A group whose other operands and accumulator seeds do not change from one group to the next is otherwise ONE expression to the
 // compiler -- the MFMA builtin is pure -- and is hoisted out of a loop or merged with its twin: the hi fragment, which the first
 // MFMA of either accumulator chain reads, is laundered per group, so every group is issued.
@@ -828,18 +816,11 @@ __device__ __forceinline__ void split_finish(EpiState& st) {
 // matters.  kind: 0 softplus(beta=100), 1 g * sigma'(z) from the stashed activation, 2 relu, 3 identity;
 // adjoint (hn_field2_*_adj): 4 forward-direction sweep  v = z sigma',  w = z (1 - sigma') * (pd.x 100 / 256)  (pd.x = dz:
 // w is the second-order source sigma'' u dzb of oracle/field_bwd.py written without a division by sigma');
-// 5 second reverse sweep  v = z sigma' + pd.x;  6 relu mask  v = pd.v > 0 ? z : 0;  7 (measurement builds, WRONG results) no
-// element-wise work at all: v = c1 and the fragments are conversions of the raw accumulators.
-#ifndef HN_DBG_SOFTPLUS_AS_RELU
-#define HN_DBG_SOFTPLUS_AS_RELU 0   // 1 (measurement only, WRONG results): the softplus epilogue issues a ReLU's instructions -- an upper bound on
-                                    // what a cheaper activation epilogue could buy the evaluation kernels (round 5, profiles/r05/README.md)
-#endif
-template <int J, int P, int KIND_, bool FRAGS, typename PD>
+// 5 second reverse sweep  v = z sigma' + pd.x;  6 relu mask  v = pd.v > 0 ? z : 0.
+template <int J, int P, int KIND, bool FRAGS, typename PD>
 __device__ __forceinline__ void pair_phase(EpiState& st, const PD& pd) {
-    constexpr int KIND = (HN_DBG_SOFTPLUS_AS_RELU && KIND_ == 0) ? 2 : KIND_;
     constexpr int i0 = 2 * J, i1 = 2 * J + 1;
-    if constexpr (P == 0 && KIND == 7) {
-    } else if constexpr (P == 0) {
+    if constexpr (P == 0) {
         const f32x2 c1 = {st.c1[i0], st.c1[i1]}, c2 = {st.c2[i0], st.c2[i1]};
         const f32x2 inv = {st.inv, st.inv};
         st.z2 = c2 * inv + c1;
@@ -870,22 +851,8 @@ __device__ __forceinline__ void pair_phase(EpiState& st, const PD& pd) {
         }
         if constexpr (KIND == 5) v = st.z2 - st.e2 + f32x2{pd.x[i0], pd.x[i1]};
         if constexpr (KIND == 6) v = f32x2{pd.v[i0] > 0.f ? st.z2[0] : 0.f, pd.v[i1] > 0.f ? st.z2[1] : 0.f};
-        if constexpr (KIND == 7) v = f32x2{st.c1[i0], st.c1[i1]};
         st.v[i0] = v[0];
         st.v[i1] = v[1];
-    } else if constexpr (KIND == 7) {
-        // (measurement only, PhRaw below: the two fragments straight from the two accumulators, one conversion per pair each)
-        if constexpr (FRAGS) {
-            constexpr int u = frag_u(i0), j = frag_j(i0);
-            unsigned p2;
-            if constexpr (P == 4) {
-                asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(p2) : "v"(st.c1[i0]), "v"(st.c1[i1]));
-                set_pair<j / 2>(st.hi[u], p2);
-            } else {
-                asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(p2) : "v"(st.c2[i0]), "v"(st.c2[i1]));
-                set_pair<j / 2>(st.lo[u], p2);
-            }
-        }
     } else if constexpr (P == 4) {
         if constexpr (FRAGS) {
             constexpr int u = frag_u(i0), j = frag_j(i0);
@@ -1140,11 +1107,6 @@ struct PhRelu {
         if constexpr (P == 0) st.v[I] = fmaxf(fmaf(st.c2[I], st.inv, st.c1[I]), 0.f);
     }
 };
-// measurement builds only (-DHN_DBG_FAR_NO_EPILOGUE=1 of the hand field, WRONG results): pair_phase kind 7
-struct PhRaw {
-    static constexpr int kind = 7;
-    static constexpr bool branchy = HN_BRANCHY_FWD;
-};
 struct PhIdentity {
     static constexpr int kind = 3;
     static constexpr bool branchy = HN_BRANCHY_FWD;
@@ -1331,33 +1293,6 @@ struct StashT {
         const f32x8 ab = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
         const f32x8 cd = __builtin_shufflevector(c, d, 0, 1, 2, 3, 4, 5, 6, 7);
         return __builtin_shufflevector(ab, cd, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-    }
-    // MEASUREMENT BUILD ONLY (-DHN_STASH_HALF=1; not parity-preserving): the same tile as 16 fp16 values, two 16-byte accesses instead
-    // of four -- what halving the a1..a7 stash traffic of the evaluation kernel would be worth.  Not written for
-    // the packed form of a uniform wave: run such a build with HONERF_UNIFORM_STASH=0 or 2.
-    __device__ __forceinline__ void tile_store_half(int slot, int t, const f32x16& y) const {
-        const int vo = fresh_voff() + (slot * SLOT_BYTES + t * 4096);
-        h8 a, b;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            a[i] = (_Float16)y[i];
-            b[i] = (_Float16)y[8 + i];
-        }
-        st16_at(a, vo);
-        st16_at(b, vo + 1024);
-    }
-    __device__ __forceinline__ f32x16 tile_load_half(int slot, int t) const {
-        const int off = slot * SLOT_BYTES + t * 4096;
-        const int vo = load_voff();
-        const h8 a = __builtin_bit_cast(h8, ld16_at(vo, off));
-        const h8 b = __builtin_bit_cast(h8, ld16_at(vo, off + 1024));
-        f32x16 y;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            y[i] = (float)a[i];
-            y[8 + i] = (float)b[i];
-        }
-        return y;
     }
     // fragment block s (byte offset `base` + s * 2 KiB): [hi | lo][lane] 16 B
     __device__ __forceinline__ void frag_store(int base, int s, const h8& hi, const h8& lo) const {

@@ -1,4 +1,4 @@
-"""The all-far tile program's reverse sweep is a discarded pass ("The reverse sweep held", HN_FAR_REV_HELD).
+"""The all-far tile program's reverse sweep is a discarded pass ("The reverse sweep held").
 Since the Jacobian pass of the all-far program multiplies zero fragments, nothing reads dz6 .. dz0: the program with the shared
 epilogue and without table chunks now fetches two of the sweep's 56 chunks, runs the other 54 groups on one held k-step with the zero
 fragment as B, runs none of the sweep's epilogues, and its forward layers keep neither a1 .. a7 nor the seed dz7 in the LDS image.
