@@ -25,6 +25,7 @@
 //   k_cd_combine  per point: minimum over the ranges -> distance
 // There are no atomics: a repeated call gives the same bits.
 #include "hn_common.h"
+#include "hn_tridist.h"
 
 namespace hn {
 namespace {
@@ -331,39 +332,7 @@ __global__ void __launch_bounds__(WN_THREADS) k_wn_combine(const float* __restri
     if (winding) winding[p] = w;
 }
 
-// squared distance from the origin to triangle (a, b, c) (relative to the point): Ericson, Real-Time Collision Detection 5.1.5,
-// the regions picked in his order by selects (lanes of a wave land in different regions)
-__device__ inline float tri_dist2(float4 a, float4 b, float4 c) {
-    const float abx = b.x - a.x, aby = b.y - a.y, abz = b.z - a.z;
-    const float acx = c.x - a.x, acy = c.y - a.y, acz = c.z - a.z;
-    // p - a = -a, p - b = -b, p - c = -c
-    const float d1 = -fmaf(abx, a.x, fmaf(aby, a.y, abz * a.z)), d2 = -fmaf(acx, a.x, fmaf(acy, a.y, acz * a.z));
-    const float d3 = -fmaf(abx, b.x, fmaf(aby, b.y, abz * b.z)), d4 = -fmaf(acx, b.x, fmaf(acy, b.y, acz * b.z));
-    const float d5 = -fmaf(abx, c.x, fmaf(aby, c.y, abz * c.z)), d6 = -fmaf(acx, c.x, fmaf(acy, c.y, acz * c.z));
-    const float vc = fmaf(d1, d4, -d3 * d2), vb = fmaf(d5, d2, -d1 * d6), va = fmaf(d3, d6, -d5 * d4);
-    // face region by default, then the edge and vertex regions override in reverse order of Ericson's tests
-    const float den = va + vb + vc;
-    const float inv = den > 0.f ? 1.f / den : 0.f;
-    float v = vb * inv, w = vc * inv;
-    const float e43 = d4 - d3, e56 = d5 - d6;
-    if (va <= 0.f && e43 >= 0.f && e56 >= 0.f) {                      // edge BC
-        w = e43 / (e43 + e56);
-        v = 1.f - w;
-    }
-    if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) {                        // edge AC
-        v = 0.f;
-        w = d2 / (d2 - d6);
-    }
-    if (d6 >= 0.f && d5 <= d6) v = 0.f, w = 1.f;                      // vertex C
-    if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) {                        // edge AB
-        v = d1 / (d1 - d3);
-        w = 0.f;
-    }
-    if (d3 >= 0.f && d4 <= d3) v = 1.f, w = 0.f;                      // vertex B
-    if (d1 <= 0.f && d2 <= 0.f) v = 0.f, w = 0.f;                     // vertex A
-    const float qx = fmaf(abx, v, fmaf(acx, w, a.x)), qy = fmaf(aby, v, fmaf(acy, w, a.y)), qz = fmaf(abz, v, fmaf(acz, w, a.z));
-    return fmaf(qx, qx, fmaf(qy, qy, qz * qz));
-}
+// tri_dist2: the squared distance from the origin to a triangle given relative to the point (hn_tridist.h, shared with hn_meshdist.hip)
 
 __global__ void __launch_bounds__(WN_THREADS) k_cd_partial(const float* __restrict__ pts, int n_points, const float* __restrict__ tv, int n_tris,
                                                            int tris_per_split, float* __restrict__ partial) {

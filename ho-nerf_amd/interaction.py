@@ -121,11 +121,12 @@ def winding_number(mesh, points):
     return _winding(m, _points(points, 'winding_number'), want_w=True)[1]
 
 
-def closest_distance(mesh, points):
+def closest_distance(mesh, points, culled=False):
     """trimesh.proximity.closest_point's distance: the unsigned distance to the nearest triangle -> float32 [P] on the device
-    (inf for a mesh without triangles)."""
+    (inf for a mesh without triangles).  culled=True asks `mesh_distance.MeshIndex` (the same arithmetic per pair behind two levels of
+    bounding boxes) instead of the brute force: the same bits."""
     m, = _meshes((mesh, 'closest_distance mesh'))
-    return _distance(m, _points(points, 'closest_distance'))
+    return _distance(m, _points(points, 'closest_distance'), culled)
 
 
 def solid_lattice(obj_mesh, hand_mesh, pitch):
@@ -149,11 +150,11 @@ def intersection_volume(obj_mesh, hand_mesh, pitch=0.005, solid=False):
     return n * pitch ** 3
 
 
-def penetration_depth(hand_mesh, obj_mesh):
+def penetration_depth(hand_mesh, obj_mesh, culled=False):
     """get_pen_depth (analys_interaction.py:44-55) -> m: the largest distance from a hand vertex inside the object mesh to the
-    object's surface; 0.0 when no hand vertex is inside."""
+    object's surface; 0.0 when no hand vertex is inside.  culled: as in closest_distance."""
     hand, obj = _meshes((hand_mesh, 'hand_mesh'), (obj_mesh, 'obj_mesh'))
-    return float(_penetration(hand, obj)[0])
+    return float(_penetration(hand, obj, culled)[0])
 
 
 def is_closed(triangles):
@@ -163,16 +164,17 @@ def is_closed(triangles):
     return bool(_closed(t, int(t.max()) + 1 if t.numel() else 0))
 
 
-def interaction_metrics(hand_mesh, obj_mesh, pitch=0.005):
+def interaction_metrics(hand_mesh, obj_mesh, pitch=0.005, culled=False):
     """get_int_vol (analys_interaction.py:21-42) on device meshes -> dict: int_vol (cm^3) and pen_dep (mm), the keys and units of the
     reference's pickle; n_obj_voxels, n_obj_voxels_inside, n_hand_verts_inside; hand_closed / obj_closed (is_closed: the metrics are
     computed on an open mesh too, but containment there is not a closed surface's).  Host syncs: the index check of both meshes,
-    the key total and torch.unique of the voxelizer, the selection of the inner hand vertices, and the final read-back."""
+    the key total and torch.unique of the voxelizer, the selection of the inner hand vertices, and the final read-back.  culled: the
+    penetration depth's distances as in closest_distance (the same bits)."""
     hand, obj = _meshes((hand_mesh, 'hand_mesh'), (obj_mesh, 'obj_mesh'))
     pitch = _pitch(pitch)
     vox = _voxelize(obj, pitch)
     n_in = _winding(hand, vox.to(torch.float32).contiguous())[0].sum()
-    pen, n_hand = _penetration(hand, obj)
+    pen, n_hand = _penetration(hand, obj, culled)
     closed = torch.stack([_closed(hand.t, hand.v.shape[0]), _closed(obj.t, obj.v.shape[0])])
     n_in, n_hand, pen, hc, oc = torch.stack([n_in.double(), n_hand.double(), pen.double(), closed[0].double(), closed[1].double()]).tolist()
     n_in, n_hand = int(n_in), int(n_hand)
@@ -224,11 +226,14 @@ def _winding(m, p, want_w=False):
     return inside.bool(), w
 
 
-def _distance(m, p):
+def _distance(m, p, culled=False):
     P, T = p.shape[0], m.t.shape[0]
     dev = p.device
     if P == 0 or T == 0:
         return torch.full((P,), float('inf'), dtype=torch.float32, device=dev)
+    if culled:
+        from .mesh_distance import MeshIndex
+        return MeshIndex(m).closest(p, want=('dist',))['dist']
     L = _lib.load()
     rows = m.rows(torch.float32)
     with torch.cuda.device(dev):
@@ -239,7 +244,7 @@ def _distance(m, p):
     return d
 
 
-def _penetration(hand, obj):
+def _penetration(hand, obj, culled=False):
     """-> (largest distance of an inner hand vertex, count of inner hand vertices), both device scalars (one host sync: the
     selection of the inner vertices)."""
     inside = _winding(obj, hand.v32)[0]
@@ -247,7 +252,7 @@ def _penetration(hand, obj):
     if inner.shape[0] == 0:
         z = torch.zeros((), dtype=torch.float32, device=hand.v.device)
         return z, z
-    return _distance(obj, inner).max(), inside.sum()
+    return _distance(obj, inner, culled).max(), inside.sum()
 
 
 def _closed(t, n_verts):

@@ -199,6 +199,11 @@ SIGNATURES = {
     'hn_meshcast_workspace_bytes': (c_sz, [ctypes.c_longlong]),
     'hn_meshcast_prepare': (c_i, [c_f, ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, c_vp, c_sz, c_vp]),
     'hn_meshcast': (c_i, [c_vp, c_sz, ctypes.c_longlong, c_f, c_f, ctypes.c_longlong, c_fl, c_fl, c_i, c_f, c_vp, c_f, c_f, c_vp]),
+    'hn_meshdist_workspace_bytes': (c_sz, [ctypes.c_longlong]),
+    'hn_meshdist_prepare': (c_i, [c_f, ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, c_vp, c_sz, c_vp]),
+    'hn_meshdist_closest': (c_i, [c_vp, c_sz, ctypes.c_longlong, c_f, ctypes.c_longlong, c_i, c_f, c_vp, c_f, c_f, c_vp]),
+    'hn_mesh_face_areas': (c_i, [c_f, ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, c_f, c_vp]),
+    'hn_mesh_sample': (c_i, [c_f, ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong, ctypes.c_uint, c_f, c_vp, c_f, c_vp]),
     'hn_meshcc_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong]),
     'hn_meshcc_measure_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong]),
     'hn_meshcc_label': (c_i, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

@@ -866,6 +866,44 @@ int hn_meshcast_prepare(const float* vertices, long long n_verts, const long lon
 int hn_meshcast(const void* workspace, size_t workspace_bytes, long long n_tris, const float* rays_o, const float* rays_d, long long n_rays, float near,
                 float far, int cull, float* t, int* face, float* bary, float* normal, hn_stream_t stream);
 
+/* ---- closest point on a triangle mesh and surface sampling (hn_meshdist.hip): what mesh-to-mesh distances are made of ---------------
+ * The rule.  Per point p and triangle (a, b, c): d2 = the squared distance from p to the triangle by Ericson's
+ * region tests (Real-Time Collision Detection 5.1.5) in fp32, the arithmetic of hn_closest_distance bit for bit (hn_tridist.h), with
+ * the barycentric pair (v, w) of the closest point a + (b - a) v + (c - a) w.  The winner is the smallest (d2, face) pair, face the
+ * index in the caller's triangle array: the result depends neither on `order`, nor on `cull`, nor on the other points of the call, and
+ * is the same bits on every run.  A zero-area triangle has a distance and can win; a triangle with a coordinate that is not finite or
+ * a vertex index outside [0, n_verts) (never dereferenced) never wins.
+ *   hn_meshdist_workspace_bytes: the workspace of a mesh of n_tris triangles (0 for n_tris outside [0, 2^31 - 65));
+ *   hn_meshdist_prepare: vertices [n_verts, 3] fp32, triangles [n_tris, 3] int64, order [n_tris] int32, a permutation of the triangles
+ *     (workspace slot s holds triangle order[s]) -> the workspace: the triangles in that order, the bounds of every block of 64 and of
+ *     every group of 32 blocks (of their finite triangles), then the scratch of the permutation check.  An order that is not a
+ *     permutation is refused (one device-to-host read of a flag: this call waits for the stream).  No atomics;
+ *   hn_meshdist_closest: points [n_points, 3] fp32 against a prepared workspace -> dist [n_points] fp32 (sqrtf of the smallest d2; inf
+ *     when no triangle has a distance), face [n_points] int32 (among triangles of equal d2 the smallest index; -1 when dist is inf),
+ *     point [n_points, 3] fp32 (p + the closest point relative to p, in tri_dist2's fmaf chain; 0 when face is -1), bary [n_points, 2]
+ *     fp32 ((v, w); 0).  Each output may be NULL: it is then not written.  cull != 0 skips the groups and blocks whose bounds are
+ *     farther than the nearest triangle can be, by lb > ub (1 + 1e-4) + 1e-4 diag^2; cull = 0 walks every block; the same bits
+ *     either way.  Every loop's trip count is fixed by n_tris alone;
+ *   hn_mesh_face_areas: area [n_tris] fp64 = |(b - a) x (c - a)| / 2 in fp64 from the fp32 vertices, normal [n_tris, 3] fp32 = the
+ *     unit normal (0 for a triangle of area 0 or not finite, whose area is 0).  Either output may be NULL;
+ *   hn_mesh_sample: n stratified surface samples: with (r0, r1, r2) the top 24 bits k of three successive splitmix64 outputs started
+ *     at the counter (seed << 32) | i, as (k + 0.5) / 2^24, sample i lies in the first triangle t whose inclusive cumulative area
+ *     cum_area[t] (fp64 [n_tris], the caller's) exceeds (i + r0) / n * cum_area[n_tris - 1], at
+ *     (1 - sqrt(r1)) a + sqrt(r1) (1 - r2) b + sqrt(r1) r2 c, all in fp64 -> points [n, 3] fp32, face [n] int32, normal [n, 3] fp32
+ *     (each may be NULL).  The same bits for the same (mesh, cum_area, n, seed).
+ * Nothing allocates; only hn_meshdist_prepare synchronises.  A NULL input, a count outside [0, 2^31 - 65), a workspace that is too
+ * small or an order that is not a permutation is HN_EINVAL with a message; n_tris = 0 or n_points = 0 launches nothing and returns 0
+ * (the outputs are left as they are). */
+size_t hn_meshdist_workspace_bytes(long long n_tris);
+int hn_meshdist_prepare(const float* vertices, long long n_verts, const long long* triangles, long long n_tris, const int* order, void* workspace,
+                        size_t workspace_bytes, hn_stream_t stream);
+int hn_meshdist_closest(const void* workspace, size_t workspace_bytes, long long n_tris, const float* points, long long n_points, int cull,
+                        float* dist, int* face, float* point, float* bary, hn_stream_t stream);
+int hn_mesh_face_areas(const float* vertices, long long n_verts, const long long* triangles, long long n_tris, double* area, float* normal,
+                       hn_stream_t stream);
+int hn_mesh_sample(const float* vertices, long long n_verts, const long long* triangles, long long n_tris, const double* cum_area, long long n,
+                   unsigned seed, float* points, int* face, float* normal, hn_stream_t stream);
+
 /* ---- connected components of a triangle mesh (hn_meshcc.hip): label, measure, keep -- Trimesh.split / .area / .volume on the device --
  * The rule.  Two triangles belong to the same component when they share a vertex index, transitively: vertex
  * connectivity (trimesh's split joins over shared edges; the two differ only at pinch vertices).  A component's label is the smallest
