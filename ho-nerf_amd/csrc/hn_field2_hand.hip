@@ -56,11 +56,10 @@ struct Hand2Args {
                 // form -- StashT::ush in its low four bits (USTASH_SHIFT); 0 = off
     int far_tiles;   // HONERF_FAR_TILES (FieldLaunchOpts::far_tiles) and the packed uniform stash, the full evaluation (MODE 1) only: a tile
                      // whose four waves are all far runs the all-far tile program (FarStash below); 0 = every tile runs the general one
-    int far_epilogue;   // HONERF_FAR_EPILOGUE (FieldLaunchOpts::far_epilogue): the all-far program computes the SDF layers' element-wise
-                        // epilogues once per row of lanes (PhFarShared below); 0 = per lane, as the general program does
-    int far_stream;   // HONERF_FAR_STREAM (FieldLaunchOpts::far_stream): the all-far program with the shared epilogue fetches no weight chunk
-                      // whose products are 0 * w or discarded (FAR_FEAT_* / FAR_JAC_* below); 0 = all-far tiles run the all-far program
-                      // that streams every chunk (per-lane epilogue)
+    int far_epilogue;   // HONERF_FAR_EPILOGUE (FieldLaunchOpts::far_epilogue) and
+    int far_stream;     // HONERF_FAR_STREAM (FieldLaunchOpts::far_stream), both on: a workgroup computes the far result in its first all-far
+                        // tile of a launch and every later all-far tile of it stores that result again (the reuse program, FAR_SAVE below:
+                        // no weight chunk, no epilogue, the tile's MFMAs on held operands); either 0 = every all-far tile computes it
     // adjoint (MODE 2): upstream gradients in, input / pose gradients out
     const float* g_sdf;    // [n]
     const float* g_grad;   // [n,3]
@@ -148,33 +147,24 @@ constexpr size_t HAND2_LDS_POSE = 2 * CHUNK_MAX + WG_WAVES * STAGE_BYTES + 16;  
 constexpr int FAR_IMAGE_BYTES = (HS_DZ4 + 1) * (SLOT_BYTES >> USTASH_SHIFT);
 static_assert(HS_A1 == 0 && HS_DZ7 == 7 && HS_FVEC == 8 && HS_DZ4 == 9 && FAR_IMAGE_BYTES == 10240 && HAND2_LDS_POSE % 16 == 0 && STAGE_BYTES >= 1024,
               "the all-far image covers the slots 0 .. HS_DZ4 and its stores' dump is the wave's staging area");
-// Behind each wave's image: the two lines of the shared epilogue (PhFarShared below) -- FAR_Z, the 32 fp32 results of one output tile
-// of lin7 (a8 has no slot in the image) in the layout of an image tile ([block q][half][4 floats]: register i of half h at
-// 32 (i >> 2) + 16 h + 4 (i & 3)), and FAR_FRAG, the tile's four B fragments per half ([half][hi 0 | hi 1 | lo 0 | lo 1], 16 bytes each: element i's hi part at 64 h + 2 i, its lo part
-// 32 bytes on -- frag_u(i) = i >> 3, frag_j(i) = i & 7 on this shape).
-constexpr int FAR_Z = FAR_IMAGE_BYTES;
-constexpr int FAR_FRAG = FAR_IMAGE_BYTES + 128;
-constexpr int FAR_WAVE_BYTES = FAR_IMAGE_BYTES + 256;
+// Behind each wave's image: FAR_SAVE, the far result of the launch as this wave computed it in the workgroup's first all-far tile --
+// [sdf | rgb 0..2] as stored to Hand2Args::sdf / rgb, then the 256 fp32 feature rows in the order of Hand2Args::feat.  For a sample
+// whose 21 masks are 0 the field is a function of the weights alone (zero features, zero gradient, and the colour network sees
+// nothing else), so every far sample of a launch gets these values: the all-far program (FAR_ = 1) writes them here, nothing else
+// does, and the reuse program stores them for every later all-far tile of the workgroup.  Every wave keeps its own copy (a wave's LDS
+// operations complete in order: no exchange between waves), and nothing survives a launch.
+constexpr int FAR_SAVE = FAR_IMAGE_BYTES;
+constexpr int FAR_SAVE_FEAT = FAR_SAVE + 16;
+constexpr int FAR_WAVE_BYTES = FAR_SAVE_FEAT + H * (int)sizeof(float);
 constexpr size_t HAND2_LDS_EVAL = HAND2_LDS_POSE + WG_WAVES * FAR_WAVE_BYTES;   // the full evaluation kernels' LDS (they keep no pose rows)
 static_assert(HAND2_LDS_EVAL <= 160 * 1024, "LDS of a CU");
-static_assert(S16 || (frag_u(9) == 1 && frag_j(9) == 1 && frag_u(7) == 0 && frag_j(7) == 7), "FAR_FRAG's element map is the 32x32x16 shape's");
+static_assert(H == 256 && FAR_WAVE_BYTES % 16 == 0, "a saved feature row is one 16-byte load per lane");
 struct FarStash {
     char* img;    // this wave's image
     char* dump;   // 1 KiB that nobody reads
     __device__ __forceinline__ void init(char* lds, int wave) {
         img = lds + HAND2_LDS_POSE + wave * FAR_WAVE_BYTES;
         dump = lds + 2 * CHUNK_MAX + wave * STAGE_BYTES;
-    }
-    // the 16 values of this lane's half of the line FAR_Z (lin7's a8 under the shared epilogue), as tile_load reads an image tile
-    __device__ __forceinline__ void line_load(float (&v)[16]) const {
-        using f32x4 = float __attribute__((ext_vector_type(4)));
-        const char* const p = img + FAR_Z + ((lane_x16() & 512) >> USTASH_SHIFT);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 x = *reinterpret_cast<const f32x4*>(p + 32 * q);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[4 * q + i] = x[i];
-        }
     }
     // where this lane stores its 16 bytes of the block at byte offset `off` (a multiple of 1 KiB) of the wave's region
     __device__ __forceinline__ char* st_at(int off) const {
@@ -218,95 +208,6 @@ struct FarStash {
     }
 };
 
-// ---- the shared epilogue of the all-far program (HONERF_FAR_EPILOGUE, Hand2Args::far_epilogue) ---------------------------------------
-// In an all-far tile the 16 values that lane (j, h) holds of an output tile do not depend on j, so the element-wise epilogue of the SDF
-// network's forward layers (softplus; the program's reverse sweep is a discarded pass and has none) and the fp16 split behind it
-// are the same 32 results computed by 32 lanes each.  Here they are computed ONCE per row of 16 lanes, one element per lane, and
-// come back to every lane through LDS:
-//   calls 0..7   every lane forms z = c2 * inv + c1, the packed fma of pair_phase, and keeps element e = j & 15 of the 16: a tree of 15
-//                v_cndmask_b32 on the four low bits of the lane number, the masks being constants in scalar registers (the first form
-//                sent z through LDS -- the j == 0 lanes stored a line of 16 z per half, every lane read one element back: four
-//                ds_write_b128 of the whole wave per tile, and came out SLOWER than per lane in the in-kernel stamps);
-//   call 10      the offset of element e = j & 15 of half h within a tile of the image's layout (what call 20 stores through);
-//   calls 16..19 one element through pair_phase's operations in scalar form (v_mul, v_exp, v_add, v_log, v_max, v_fma: the packed
-//                forms round each half as these do);
-//   call 20      LINE (lin7, whose `fin` reads all 16): the fp32 result to its element's cell of the line FAR_Z (the lanes j and j ^ 16
-//                store the same bits to the same cell); the other layers' a_l are kept nowhere: nothing reads them;
-//   calls 21, 22 split_pair_hi / split_pair_lo's instructions on the one value, the two halves to FAR_FRAG;
-//   call 28      every lane reads the tile's four fragments, four broadcast ds_read_b128.
-// A wave's LDS operations complete in order, so nothing but program order stands between a line's store and its read.  The calls sit
-// in the MFMA slots of the next tile like pair_phase's (Epi::run); the lane offsets are formed where they are used (lane_x16()).
-// lane bit B set ? b : a -- one v_cndmask_b32 whose mask is a constant (no v_cmp, nothing live across the tile)
-template <int B>
-__device__ __forceinline__ float lane_bit_select(float a, float b) {
-    constexpr unsigned long long M = B == 0 ? 0xAAAAAAAAAAAAAAAAull : (B == 1 ? 0xCCCCCCCCCCCCCCCCull : (B == 2 ? 0xF0F0F0F0F0F0F0F0ull : 0xFF00FF00FF00FF00ull));
-    float r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(M));
-    return r;
-}
-template <bool LINE>   // softplus; LINE: the fp32 results go to the line FAR_Z
-struct PhFarShared {
-    static constexpr bool own_calls = true;
-    static constexpr int kind = 0;
-    static constexpr bool branchy = HN_BRANCHY_FWD;
-    char* img;
-    float z, x, v;       // carried from call to call of one tile
-    float g[8];          // the select tree of calls 0..7
-    unsigned hp, lp;
-    char* pe;
-    template <int C, bool FRAGS, typename PD>
-    __device__ __forceinline__ void call(EpiState& st, const PD&) {
-        if constexpr (C < 8) {
-            constexpr int i0 = 2 * C, i1 = 2 * C + 1;
-            const f32x2 c1 = {st.c1[i0], st.c1[i1]}, c2 = {st.c2[i0], st.c2[i1]};
-            const f32x2 inv = {st.inv, st.inv};
-            const f32x2 z2 = c2 * inv + c1;
-            g[C] = lane_bit_select<0>(z2[0], z2[1]);
-            if constexpr ((C & 1) == 1) g[C - 1] = lane_bit_select<1>(g[C - 1], g[C]);
-            if constexpr ((C & 3) == 3) g[C - 3] = lane_bit_select<2>(g[C - 3], g[C - 1]);
-            if constexpr (C == 7) z = lane_bit_select<3>(g[0], g[4]);
-        } else if constexpr (C == 10) {
-            // (formed in every tile, kept or not: lane_x16() is an asm volatile, and its three instructions are part of the device code
-            //  as it stands)
-            const int l16 = lane_x16();   // 512 h + 16 j -> 32 (e >> 2) + 16 h + 4 (e & 3), e = j & 15
-            pe = img + (((l16 & 0xC0) >> 1) | ((l16 >> 5) & 16) | ((l16 >> 2) & 12));
-        } else if constexpr (C == 16) {
-            x = z * K100_;
-        } else if constexpr (C == 17) {
-            x = __builtin_amdgcn_exp2f(-fabsf(x));
-        } else if constexpr (C == 18) {
-            x = __builtin_amdgcn_logf(x + 1.f);
-        } else if constexpr (C == 19) {
-            v = x * C100_ + fmaxf(z, 0.f);
-        } else if constexpr (C == 20) {
-            if constexpr (LINE) *reinterpret_cast<float*>(pe + FAR_Z) = v;
-        } else if constexpr (C == 21) {
-            if constexpr (FRAGS) {
-                float r;   // (the instructions of split_pair_hi / split_pair_lo, both members of the pair being this value)
-                asm("v_cvt_pk_f16_f32 %0, %3, %3\n\t"
-                    "v_fma_mix_f32 %1, %0, -1.0, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
-                    "v_fma_mixlo_f16 %2, %1, %4, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]"
-                    : "=&v"(hp), "=&v"(r), "=&v"(lp)
-                    : "v"(v), "v"(st.scale));
-            }
-        } else if constexpr (C == 22) {
-            if constexpr (FRAGS) {
-                char* const p = img + FAR_FRAG + ((lane_x16() >> 3) & 94);   // 64 h + 2 (j & 15)
-                *reinterpret_cast<unsigned short*>(p) = (unsigned short)hp;
-                *reinterpret_cast<unsigned short*>(p + 32) = (unsigned short)lp;
-            }
-        } else if constexpr (C == 28) {
-            if constexpr (FRAGS) {
-                const char* const p = img + FAR_FRAG + ((lane_x16() >> 3) & 64);
-                st.hi[0] = *reinterpret_cast<const h8*>(p);
-                st.hi[1] = *reinterpret_cast<const h8*>(p + 16);
-                st.lo[0] = *reinterpret_cast<const h8*>(p + 32);
-                st.lo[1] = *reinterpret_cast<const h8*>(p + 48);
-            }
-        }
-    }
-};
-
 constexpr int HB_HID = chunk_bytes(1, 16, true);
 constexpr int HB_BWD = chunk_bytes(1, 16, false);
 constexpr int HB_BONE = chunk_bytes(4, 4, false);
@@ -315,40 +216,12 @@ constexpr int HB_LEFT_T = chunk_bytes(4, KS_LEFT, true);    // leftover chunk wi
 constexpr int HB_LEFT = chunk_bytes(4, KS_LEFT, false);
 constexpr int HB_G = chunk_bytes(4, 2, true);         // colour lin0: enc(g) columns + the 4 biases
 constexpr int HB_W4ROWS = 3 * TAIL_BYTES;             // adjoint: the three rows of colour lin4, one tail-format KiB each
-
-// ---- the all-far program's weight stream (HONERF_FAR_STREAM, Hand2Args::far_stream; the instance with the shared epilogue) ------------
-// In an all-far tile the B operand of every MFMA over the feature space is the zero fragment (lin0, the lin4 skip columns, colour
-// lin0's feature columns: C += W * 0) or its result is discarded (the Jacobian pass).  The MFMAs run (dense compute), but on ONE
-// k-step of a chunk that is read into registers once per pass (mma_held in hn_mlp2.h); the Jacobian pass's B operand is the zero
-// fragment too.  Chunk by chunk against build_hand_stream (hn_pack2.hip), the "table" chunks below are exactly those that carry
-// nothing else the tile reads --
-//   feature_block:       per bone two chunks B.chunk(M, .., 4, 4, .., nullptr), HB_BONE, no tail: TABLE.  Then the two leftover chunks,
-//                        whose tail holds lin0's biases (lin4, colour lin0: no tail, but 12 k-step blocks of their own size that the
-//                        code behind the bones acquires, and the fetch of what follows is issued from them): FETCHED, where they are.
-//   feature_rows_T_adj:  4 chunks B.chunk(M, true, .., 1, 16, .., nullptr) of the leftover block, then 4 per bone, HB_BWD, no tail: TABLE.
-//   everything else (the hidden, reverse and colour layers, lin4's hidden part, colour lin0's feature-vector tiles and its enc(g)
-//   chunks with the biases): FETCHED.
-// Of a pass's table chunks the first two are still fetched: the one that is in flight when the pass starts (the code in front of the
-// pass is shared with the other instances) and the one behind it, whose first k-step is the held one.  With that chunk in the
-// SECOND buffer of the pass, the first real chunk behind the table lands in the buffer, and leaves ws.phase at the value, that the
-// full stream gives it (an even number of table chunks is skipped), so the code behind a pass is the other instances' code.
-// The REVERSE SWEEP is a pass of the same kind although its chunks are no table: with the Jacobian pass on zero fragments nothing
-// reads dz6 .. dz0, so the sweep's 56 products (W7^T .. W1^T, 8 tiles each, one HB_BWD chunk per tile, no tail) are discarded as
-// well.  Its first two chunks are fetched, the other 54 are not; its groups multiply the zero fragment and run no epilogue, and the
-// forward layers keep neither a1 .. a7 nor the seed dz7 for it.  (discarded_pass in the kernel is the protocol of all three.)
-constexpr int FAR_FEAT_TABLE = 2 * N_BONES;        // table chunks of a feature pass
-constexpr int FAR_JAC_TABLE = 4 * (N_BONES + 1);   // ... of the Jacobian pass
-constexpr int FAR_REV_TABLE = 7 * 8;               // chunks of the reverse sweep, discarded with the Jacobian pass's
-constexpr int FAR_TABLE_FETCHED = 2;               // of each pass's table: the chunk in flight and the one whose k-step 0 is held
-constexpr int FAR_STREAM_SKIPPED = 3 * (FAR_FEAT_TABLE - FAR_TABLE_FETCHED) * HB_BONE + (FAR_JAC_TABLE - FAR_TABLE_FETCHED) * HB_BWD;   // bytes per tile
-static_assert(HB_BONE == 4 * 4 * KS_BYTES && HB_BWD == 16 * KS_BYTES,
-              "a table chunk is k-step blocks from end to end: every byte an MFMA reads as A is a packed [hi | lo] fragment, never an fp32 tail");
-static_assert((FAR_FEAT_TABLE - FAR_TABLE_FETCHED) % 2 == 0 && (FAR_JAC_TABLE - FAR_TABLE_FETCHED) % 2 == 0,
-              "an even number of chunks is skipped: buffer parity behind the pass is the full stream's");
-static_assert(FAR_STREAM_SKIPPED == 120 * HB_BONE + 86 * HB_BWD, "6.75 MB of the 12.4 MB a tile streams");
-constexpr int FAR_REV_SKIPPED = (FAR_REV_TABLE - FAR_TABLE_FETCHED) * HB_BWD;   // bytes per tile
-static_assert((FAR_REV_TABLE - FAR_TABLE_FETCHED) % 2 == 0 && FAR_REV_SKIPPED == 54 * HB_BWD,
-              "an even number of the sweep's chunks is skipped too: 1.77 MB of the 5.6 MB that were left");
+// chunks of a full evaluation tile, in the stream's order: lin0's feature pass (per bone two chunks, two leftover chunks), lin1-3 and
+// lin4's hidden part, lin4's feature pass, lin5-8, the reverse sweep, the Jacobian pass (four chunks for the leftover block, four per
+// bone), colour lin0 (feature-vector tiles, feature pass, two enc(g) chunks), colour lin1-3
+constexpr int TILE_CHUNKS = (2 * N_BONES + 2) + 4 * 8 + (2 * N_BONES + 2) + 4 * 8 + 7 * 8 + 4 * (N_BONES + 1) + 8 + (2 * N_BONES + 2) + 2 + 3 * 8;
+constexpr int REUSE_FETCHED = 2;   // of them, what the reuse program fetches: the chunk in flight at the tile's start and the one whose k-step 0 it holds
+static_assert(HB_BONE == 4 * 4 * KS_BYTES, "a bone chunk is k-step blocks from end to end: every byte an MFMA reads as A is a packed [hi | lo] fragment, never an fp32 tail");
 
 struct Bone2 {
     float v, r[3], hh;
@@ -669,6 +542,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
     XcdPace xp;
     xp.init(a.xsync);
     const int full_rounds = n_tiles / (int)gridDim.x;
+    [[maybe_unused]] bool have_far = false;   // this workgroup's FAR_SAVE holds the far result of this launch (workgroup-uniform)
     float* const prow = reinterpret_cast<float*>(lds + HAND2_LDS_POSE) + wave * (POSE_FRAMES * POSE_ROW);   // this wave's pose-gradient sums per frame (adjoint modes)
     for (int tile = blockIdx.x, it = 0; tile < n_tiles; tile += gridDim.x, ++it) {
         if constexpr (RUN_ADJ) {
@@ -750,8 +624,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         // plus bone 0, whose first chunk is always in flight when a pass starts.
         // far (a kernel with the all-far program): no wave of this tile has a live bone, by the kernel's own masks, in a dense launch
         // that asked for it -- the workgroup runs the tile with the all-far program.  One choice per tile, workgroup-uniform: the
-        // programs hand the weight stream to one another in the same state (offset, buffer, the chunk in flight) at every tile end,
-        // and between the passes over the feature space, where the all-far program of HONERF_FAR_STREAM fetches less of it.
+        // programs hand the weight stream to one another in the same state (offset, buffer, the chunk in flight) at every tile end.
         // (A kernel without that program exchanges the masks where it always did, behind the leftover block and for a culled launch alone.)
         unsigned nzw_w = (1u << N_BONES) - 1u;
         bool far = false;
@@ -764,13 +637,181 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             far = nz_any == 0u && a.cull == 0 && a.far_tiles != 0;
         }
         // the tile program from here on: FAR_ = the all-far instance (returns true where a phase-timing build leaves the kernel)
-        // (FAR_ = 2, LEAN: the all-far instance with the shared epilogue, PhFarShared, that fetches no table chunk of the stream
-        //  (FAR_FEAT_TABLE / FAR_JAC_TABLE above) and whose reverse sweep is a discarded pass (FAR_REV_TABLE): nothing is kept for the
-        //  sweep, so the forward layers' epilogues have no slot of the image to store a_l to;
-        //  FAR_ = 1: per-lane epilogue, full stream -- where HONERF_FAR_EPILOGUE or HONERF_FAR_STREAM is 0)
+        // (FAR_ = 1: the all-far program -- full stream, per-lane epilogue, the real reverse sweep -- which computes the far result and
+        //  leaves it in FAR_SAVE;  FAR_ = 2: the reuse program, for a workgroup that has that result)
         auto program = [&](auto FAR_) __attribute__((always_inline)) -> bool {
         constexpr bool FAR = decltype(FAR_)::value != 0;
-        constexpr bool LEAN = decltype(FAR_)::value == 2;
+        constexpr bool REUSE = decltype(FAR_)::value == 2;
+        if constexpr (REUSE) {
+        // ---- the reuse program: an all-far tile of a workgroup whose FAR_SAVE holds the launch's far result ----------------------------
+        // It stores that result for its samples and issues the tile's MFMAs (dense compute), every one of them a discarded product:
+        // A is ONE k-step held in 8 VGPRs (mma_held launders it per group, so every group is issued), B the two run-time zero
+        // fragments, the accumulators start from zero and the results go to an empty asm.  No epilogue, no stash, no LDS image.
+        // One group per chunk of the full stream, in the stream's order and with each pass's static shape -- where the other programs
+        // unroll a tile it unrolls a held group, and its four loops are theirs -- so a timing build still records TILE_CHUNKS chunk
+        // starts per tile and the kernel keeps the dense program's MFMA count (tests/test_far_hold_isa.py).
+        // The weight stream: the tile's first two chunks are fetched (bone 0's two chunks of lin0: k-step blocks from end to end, the
+        // static_assert at HB_BONE, so the held k-step is finite) and no other.
+        //   entry    the tile's first chunk is in flight to buffer X (begun by the tile before, or in front of the tile loop); ws.phase = Y
+        //   group 0  acquire: X landed.  The second chunk -> Y, its pieces in this group's slots.  MFMAs read X: the last read of X.
+        //   group 1  acquire: Y landed, and every wave is past its last read of X.  k-step 0 of Y -> the held registers: the last read
+        //            of Y, returned long before this wave reaches the next barrier, the first acquire of the next tile, behind which
+        //            alone something is fetched into Y again.
+        //   colour lin3, if `more`: the NEXT tile's first chunk -> X, from stream offset 0, where every program fetches it.
+        //   exit     ws.goff = HB_BONE, ws.phase = Y and the next tile's first chunk in flight to X if `more`; nothing in flight and
+        //            nothing fetched since group 0 if not: the state in which every program leaves the stream.  Two fetches per
+        //            tile instead of TILE_CHUNKS, an even number both, so ws.phase comes out as the full stream leaves it.
+        static_assert(TILE_CHUNKS == 374 && (TILE_CHUNKS - REUSE_FETCHED) % 2 == 0 && REUSE_FETCHED == 2,
+                      "an even number of chunks is skipped: buffer parity at the tile's end is the full stream's");
+        ws.stamp(8);
+        ws.stamp(9);
+        using f32x4 = float __attribute__((ext_vector_type(4)));
+        h8 zh[16], zl[16];   // two run-time zeros, hi and lo: with one, the first MFMAs of a group's two accumulators are one expression,
+        {                    // and literal zeros as B operands cost hundreds of spilled registers
+            h8 z;
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) z[jj] = (_Float16)0.f;
+            asm volatile("" : "+v"(z));
+            h8 z2 = z;
+            asm volatile("" : "+v"(z2));
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                zh[s] = z;
+                zl[s] = z2;
+            }
+        }
+        HeldA held;
+        // the results of MFMAs that run for the dense count.  A single-pass product never touches its second accumulator, which is
+        // then not sunk: its 16 registers of zeros per group end up as spills in the general program's loops (profiles/r14)
+        auto sink = [](auto PS_, const f32x16& c1, const f32x16& c2) {
+            if constexpr (decltype(PS_)::value == 3)
+                asm volatile("" ::"v"(c1), "v"(c2));
+            else
+                asm volatile("" ::"v"(c1));
+        };
+        // one output tile of 16 k-steps (a chunk of a hidden, reverse or colour layer) on the held k-step
+        auto tile_group = [&](auto PS_) __attribute__((always_inline)) {
+            f32x16 r1 = zero16(), r2 = zero16();
+            ws.held();
+            mma_held<1, 16, decltype(PS_)::value>(ws, held, zh, zl, &r1, &r2);
+            sink(PS_, r1, r2);
+        };
+        auto layer = [&](auto PS_) __attribute__((always_inline)) { static_for<8>([&](auto) { tile_group(PS_); }); };
+        // a pass over the feature space: per bone two groups of 4 tiles x 4 k-steps, then the two leftover groups, onto 8 accumulators
+        // (FIRST_: lin0, whose first two groups open the tile -- the protocol above)
+        auto feature_groups = [&](auto PS_, auto FIRST_) __attribute__((always_inline)) {
+            constexpr int PS = decltype(PS_)::value;
+            f32x16 c1[8], c2[8];
+#pragma unroll
+            for (int ti = 0; ti < 8; ++ti) {
+                c1[ti] = zero16();
+                c2[ti] = zero16();
+            }
+            if constexpr (decltype(FIRST_)::value) {
+                const char* buf = ws.template acquire<0>();
+                ws.template begin_c<HB_BONE>();
+                mma_chunk<4, 4, HB_BONE, PS>(ws, buf, zh, zl, &c1[0], &c2[0], lane);
+                buf = ws.template acquire<0>();
+                held = held_load(buf);
+                mma_held<4, 4, PS>(ws, held, zh, zl, &c1[4], &c2[4]);
+            } else {
+                ws.held();
+                mma_held<4, 4, PS>(ws, held, zh, zl, &c1[0], &c2[0]);
+                ws.held();
+                mma_held<4, 4, PS>(ws, held, zh, zl, &c1[4], &c2[4]);
+            }
+#pragma unroll 1
+            for (int b = 1; b < N_BONES; ++b) {
+                ws.held();
+                mma_held<4, 4, PS>(ws, held, zh, zl, &c1[0], &c2[0]);
+                ws.held();
+                mma_held<4, 4, PS>(ws, held, zh, zl, &c1[4], &c2[4]);
+            }
+            static_for<2>([&](auto BLK) {
+                ws.held();
+                mma_held<4, KS_LEFT, PS>(ws, held, zh, zl, &c1[4 * decltype(BLK)::value], &c2[4 * decltype(BLK)::value]);
+            });
+#pragma unroll
+            for (int ti = 0; ti < 8; ++ti) sink(PS_, c1[ti], c2[ti]);
+        };
+        using BTrue = std::integral_constant<bool, true>;
+        using BFalse = std::integral_constant<bool, false>;
+        using IPH = std::integral_constant<int, PH>;
+        using IPJ = std::integral_constant<int, PJ>;
+        feature_groups(IPF{}, BTrue{});   // lin0
+        // The stores, here: behind the tile's two acquires, so that they complete under the MFMAs and no s_waitcnt vmcnt(0) finds them.
+        // The gradient is the +0 that the all-far program writes.  A feature row is one 1 KiB store of the wave per sample.
+        {
+            const f32x4 sv = *reinterpret_cast<const f32x4*>(shf.img + FAR_SAVE);
+            if (valid && h == 0) {
+                a.sdf[n] = sv[0];
+                a.grad[3 * n] = 0.f;
+                a.grad[3 * n + 1] = 0.f;
+                a.grad[3 * n + 2] = 0.f;
+                a.rgb[3 * n] = sv[1];
+                a.rgb[3 * n + 1] = sv[2];
+                a.rgb[3 * n + 2] = sv[3];
+            }
+            if (a.feat != nullptr) {
+                const f32x4 row = *reinterpret_cast<const f32x4*>(shf.img + FAR_SAVE_FEAT + 16 * lane);
+                const int n0 = tile * WG_SAMPLES + wave * 32;
+                const int cnt = n_pts - n0 < 32 ? n_pts - n0 : 32;   // (wave-uniform; <= 0: a wave of pad lanes)
+#pragma unroll 1
+                for (int s = 0; s < cnt; ++s) *reinterpret_cast<f32x4*>(a.feat + (size_t)(n0 + s) * H + 4 * lane) = row;
+            }
+        }
+        layer(IPH{});   // lin1
+        layer(IPH{});   // lin2
+        layer(IPH{});   // lin3
+        layer(IPH{});   // lin4's hidden part
+        feature_groups(IPF{}, BFalse{});   // ... and its skip columns
+        layer(IPH{});   // lin5
+        layer(IPH{});   // lin6
+        layer(std::integral_constant<int, P7>{});   // lin7
+        layer(IPH{});   // lin8
+        static_for<7>([&](auto) { layer(IPH{}); });   // the reverse sweep, W7^T .. W1^T
+        // the Jacobian pass: per tile a "dz0" group and a "dz4" group onto one pair of accumulators; the leftover block's two tiles,
+        // then two tiles per bone
+        auto jac_tile = [&]() __attribute__((always_inline)) {
+            f32x16 g1 = zero16(), g2 = zero16();
+            ws.held();
+            mma_held<1, 16, PJ>(ws, held, zh, zl, &g1, &g2);
+            ws.held();
+            mma_held<1, 16, PJ>(ws, held, zh, zl, &g1, &g2);
+            sink(IPJ{}, g1, g2);
+        };
+        jac_tile();
+        jac_tile();
+#pragma unroll 1
+        for (int b = 0; b < N_BONES; ++b) {
+            jac_tile();
+            jac_tile();
+        }
+        layer(IPC{});   // colour lin0: the feature-vector tiles,
+        feature_groups(IPC{}, BFalse{});   // the feature columns
+        static_for<2>([&](auto) {          // and the two enc(g) chunks (three passes in either precision)
+            f32x16 c1[4], c2[4];
+#pragma unroll
+            for (int ti = 0; ti < 4; ++ti) {
+                c1[ti] = zero16();
+                c2[ti] = zero16();
+            }
+            ws.held();
+            mma_held<4, 2, 3>(ws, held, zh, zl, c1, c2);
+#pragma unroll
+            for (int ti = 0; ti < 4; ++ti) sink(IP3{}, c1[ti], c2[ti]);
+        });
+        layer(IPC{});   // colour lin1
+        layer(IPC{});   // colour lin2
+        if (more) {     // colour lin3, with the next tile's first chunk on its way as in every program
+            ws.template begin_at_c<HB_BONE>(0);
+            ws.template pieces_all_c<HB_BONE>();
+            layer(IPC{});
+        } else {
+            layer(IPC{});
+        }
+        return false;
+        } else {   // the programs that compute
         const unsigned nz = FAR ? 0u : nz_w;
         unsigned nzw = FAR ? (1u << N_BONES) - 1u : nzw_w;
         auto& sh = [&]() -> auto& {
@@ -871,35 +912,6 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         };
         auto to_regs = [&](h8(&oh)[16], h8(&ol)[16]) { return to_regs_keep(KeepNo{}, oh, ol, 0); };
 
-        // ---- the chunk protocol of a discarded pass (the lean all-far program; FAR_FEAT_TABLE / FAR_REV_TABLE / FAR_JAC_TABLE above) ----
-        // A pass of TABLE chunks whose products are +-0 or discarded fetches its first two chunks, CB bytes each, and none of the others:
-        //   entry    the pass's first chunk is in flight to buffer X (begun by the code in front of the pass); ws.phase = Y
-        //   group 0  acquire: X landed.  The second chunk -> Y, its pieces in this group's slots.  MFMAs read X.
-        //   group 1  acquire: Y landed, and every wave has read X for the last time -- so the next chunk of the stream that is NEEDED,
-        //            the one TABLE chunks on from the pass's first, goes to X here, at its own offset and at the size the full stream
-        //            fetches it with (CB; where the chunk is shorter the caller's group 1 corrects ws.goff), and has the whole pass to
-        //            land.  k-step 0 of Y goes into registers: the HeldA returned.  MFMAs read Y.
-        //   the other groups  are the caller's, ws.held() + mma_held on that k-step: they read nothing.  Nothing is fetched into Y
-        //            while they run: the next fetch into Y is issued behind the first acquire after the pass, whose barrier every
-        //            wave reaches after the pass's last group.
-        //   exit     ws.goff = TABLE + 1 chunks on from the pass's first, ws.phase = Y, the next needed chunk in X: the full stream's
-        //            state behind the pass, so the code behind a pass is the other instances' code.
-        // group(G, buf) issues the MFMAs of group G = 0, 1 on the chunk at buf, with the DMA pieces of a CB-byte fetch in their slots.
-        // A chunk of these passes is packed finite fp16 from end to end (the static_assert at FAR_STREAM_SKIPPED), so the held k-step
-        // is finite, and a finite value times the zero fragment is +-0 whichever weight it is.
-        [[maybe_unused]] auto discarded_pass = [&](auto CB_, auto TABLE_, auto&& group) __attribute__((always_inline)) -> HeldA {
-            constexpr int CB = decltype(CB_)::value, TABLE = decltype(TABLE_)::value;
-            const int first = ws.goff - CB;   // stream offset of the pass's first chunk (in flight)
-            const char* buf = ws.template acquire<0>();
-            ws.template begin_c<CB>();
-            group(std::integral_constant<int, 0>{}, buf);
-            buf = ws.template acquire<0>();
-            HeldA held = held_load(buf);
-            ws.template begin_at_c<CB>(first + TABLE * CB);
-            group(std::integral_constant<int, 1>{}, buf);
-            return held;
-        };
-
         // ---- NB blocks of 4 output tiles over the feature space: per bone NB chunks (4 tiles x 4 k-steps each)
         //      sharing the bone's fragments, then NB leftover chunks (4 tiles x 3 k-steps [+ tail: the 4 biases,
         //      added here when BIAS]).  c1/c2[4 blk + ti] += W[tile, features] * feat.  Bone b+1's fragments are
@@ -992,40 +1004,6 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     }
                 });
             };
-            if constexpr (LEAN) {
-                // The all-far program that fetches no table chunk (FAR_FEAT_TABLE): the 42 bone chunks' MFMAs multiply the zero fragment,
-                // so all but bone 0's two chunks are neither fetched nor waited for (discarded_pass: 42 groups, the chunk needed
-                // next is the FIRST LEFTOVER chunk, shorter than a bone chunk; the second leftover chunk's fetch into Y is issued by
-                // the code below behind ITS acquire).  On exit ws.goff = base + 42 HB_BONE + left_bytes: the full stream's state
-                // behind its 21st bone, so the leftover blocks below are the other instances' code.
-                // The accumulators are those of the full stream, group for group: bone b's chunk blk adds 4 x 4 k-steps of (+-0) to
-                // c[4 blk .. 4 blk + 3] (signed zeros: DESIGN.md 3.1, "HONERF_FAR_STREAM").  The same bits come out with the held
-                // k-step (k-step 0 of the first tile of bone 0's second chunk) as A: +-0 onto an accumulator that is not -0 leaves
-                // it as it was ("Signed zeros").
-                static_assert(NB == 2 && left_bytes <= HB_BONE && FAR_FEAT_TABLE == NB * N_BONES, "the chunk plan of the 32x32x16 shape");
-                load_bone(N_BONES, fh[0], fl[0]);   // one zero fragment: every bone's and the leftover block's
-                {
-                    // ... and a second one for the lo parts: with ONE run-time value as both B operands, lin0's first two MFMAs of a
-                    // tile (A_hi x hi and A_hi x lo onto accumulators of 0, in groups 0 and 1, outside the loop) are one expression
-                    // and the compiler keeps one of them -- 8 MFMAs short of the dense count per tile
-                    h8 zl = fl[0][0];
-                    asm volatile("" : "+v"(zl));
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) fl[0][s] = zl;
-                }
-                HeldA held = discarded_pass(std::integral_constant<int, HB_BONE>{}, std::integral_constant<int, FAR_FEAT_TABLE>{}, [&](auto BLK, const char* buf) {
-                    constexpr int blk = decltype(BLK)::value;
-                    if constexpr (blk == 1) ws.goff += left_bytes - HB_BONE;
-                    mma_chunk<4, 4, HB_BONE, PS>(ws, buf, fh[0], fl[0], &c1[ACC_BLK * blk], &c2[ACC_BLK * blk], lane);
-                });
-#pragma unroll 1
-                for (int b = 1; b < N_BONES; ++b) {
-                    ws.held();
-                    mma_held<4, 4, PS>(ws, held, fh[0], fl[0], &c1[0], &c2[0]);
-                    ws.held();
-                    mma_held<4, 4, PS>(ws, held, fh[0], fl[0], &c1[ACC_BLK], &c2[ACC_BLK]);
-                }
-            } else {
             load_bone(0, fh[0], fl[0]);
             unsigned rem = nzw & ~1u;
             // two steps per trip with the fragment buffers swapped, NOT one step plus a copy: with a copy at the end
@@ -1053,7 +1031,6 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                     fl[0][s4] = fl[1][s4];
                 }
             }
-            }   // the bone chunks of the full stream
             static_for<NB>([&](auto BLK) {
                 constexpr int blk = decltype(BLK)::value;
                 const char* buf = ws.template acquire<0>();
@@ -1093,23 +1070,9 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         using I8t = std::integral_constant<int, 8>;
         using BTrue = std::integral_constant<bool, true>;
         using BFalse = std::integral_constant<bool, false>;
-        // The SDF network's softplus layers by program instance: the lean all-far program computes the epilogue once per lane row and
-        // keeps no a_l (its reverse sweep is discarded); the others compute it per lane and keep a_{slot + 1} for the sweep.
-        auto sp_phase = [&]() {
-            if constexpr (LEAN)
-                return PhFarShared<false>{shf.img};
-            else
-                return PhSoftplus{};
-        };
-        auto sp_fin = [&](h8(&oh)[16], h8(&ol)[16], int slot) {
-            if constexpr (LEAN)
-                return to_regs(oh, ol);
-            else
-                return to_regs_keep(KeepFull{}, oh, ol, HS_A1 + slot);
-        };
         // a hidden layer (one chunk per output tile, the bias in its tail): in -> out
         auto hidden = [&](h8(&ih)[16], h8(&il)[16], h8(&oh)[16], h8(&ol)[16], int slot) __attribute__((always_inline)) {
-            run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ih, il, lane, h, no_pre, sp_phase(), sp_fin(oh, ol, slot), no_store);
+            run_layer_c<8, 16, 1, true, true, HB_HID, HB_HID, PH>(ws, ih, il, lane, h, no_pre, PhSoftplus{}, to_regs_keep(KeepFull{}, oh, ol, HS_A1 + slot), no_store);
         };
 
         float g[3] = {0.f, 0.f, 0.f}, rgb[3] = {0.f, 0.f, 0.f}, rgb1[3] = {0.f, 0.f, 0.f};
@@ -1130,7 +1093,7 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 c2[ti] = zero16();
             }
             feature_pass(I2{}, BTrue{}, c1, c2, std::integral_constant<int, HB_LEFT_T>{}, std::integral_constant<int, HB_HID>{}, IPF{});
-            block_epilogue(I8t{}, c1, c2, sp_phase(), sp_fin(ah, al, 0));
+            block_epilogue(I8t{}, c1, c2, PhSoftplus{}, to_regs_keep(KeepFull{}, ah, al, HS_A1 + 0));
         }
         hidden(ah, al, bh, bl, 1);   // lin1
         hidden(bh, bl, ah, al, 2);   // lin2
@@ -1152,27 +1115,20 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                 mma_tile<16, 0, nbytes, PH>(ws, buf, bh, bl, c1[ti], c2[ti], lane);
             });
             feature_pass(I2{}, BFalse{}, c1, c2, std::integral_constant<int, HB_LEFT>{}, std::integral_constant<int, HB_HID>{}, IPF{});
-            block_epilogue(I8t{}, c1, c2, sp_phase(), sp_fin(ah, al, 4));
+            block_epilogue(I8t{}, c1, c2, PhSoftplus{}, to_regs_keep(KeepFull{}, ah, al, HS_A1 + 4));
         }
         hidden(ah, al, bh, bl, 5);   // lin5
         hidden(bh, bl, ah, al, 6);   // lin6
         // ---- lin7 -> a8; sdf = W8[0,:] a8 + b8; seed of the reverse sweep dz7 = sigma'(z7) W8[0,:] (scaled)
         float sdf_acc = 0.f, sdf_acc1 = 0.f;   // (16x16x32: the lane's registers of column block 0 / 1 are two samples)
         auto lin7 = [&](auto NA_) {   // NA_: the size of the chunk that follows the layer, a constant
-        // (the shared epilogue leaves a8's tile in the line FAR_Z: every lane needs its 16 values for the sdf row and the seed)
         run_layer_c<8, 16, 1, true, true, HB_HID, decltype(NA_)::value, P7>(
             ws, ah, al, lane, h,
             [&](auto, const char* tail) { return Act{tail_tile(tail, 1, h)}; },
-            [&]() {
-                if constexpr (LEAN)
-                    return PhFarShared<true>{shf.img};
-                else
-                    return PhSoftplus{};
-            }(),
+            PhSoftplus{},
             [&](auto T, EpiState& st, const auto& w8) {
                 constexpr int t = decltype(T)::value;
                 asm volatile("" : "+v"(st.hi[0]), "+v"(st.lo[0]), "+v"(st.hi[1]), "+v"(st.lo[1]));
-                if constexpr (LEAN) shf.line_load(st.v);
                 f32x16 dz;
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
@@ -1180,18 +1136,16 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
                         sdf_acc1 = fmaf(w8.v[i], st.v[i], sdf_acc1);
                     else
                         sdf_acc = fmaf(w8.v[i], st.v[i], sdf_acc);
-                    if constexpr (!LEAN) dz[i] = dsoftplus_from_act(st.v[i]) * w8.v[i] * BWD_SCALE;
+                    dz[i] = dsoftplus_from_act(st.v[i]) * w8.v[i] * BWD_SCALE;
                 }
                 if (FULL) {
                     bh[2 * t] = st.hi[0];   // a8 feeds lin8
                     bl[2 * t] = st.lo[0];
                     bh[2 * t + 1] = st.hi[1];
                     bl[2 * t + 1] = st.lo[1];
-                    if constexpr (!LEAN) {   // (the seed of a sweep that is discarded is not formed)
                     Frags f;
                     split_tile(dz, f.hi[0], f.lo[0], f.hi[1], f.lo[1]);
                     stash_frags(HS_DZ7)(T, f);
-                    }
                     if constexpr (ADJ) {
                         sh.tile_store(HS_A8, t, st.vec());
                         sh.tile_store(HS_DZ + 7, t, dz);
@@ -1221,6 +1175,18 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             ws, bh, bl, lane, h, no_pre, PhIdentity{},
             [&](auto T, EpiState& st, const auto&) {
                 constexpr int t = decltype(T)::value;
+                if constexpr (FAR) {
+                    // the feature rows of the far result (FAR_SAVE): registers 4 q .. 4 q + 3 are the rows 32 t + 8 q + 4 h + (0 .. 3) of
+                    // a.feat (tile_row).  Every lane of a half holds the same 16 values and stores them to the same cells: no branch
+                    // and no EXEC change inside the MFMA stream
+                    using f32x4 = float __attribute__((ext_vector_type(4)));
+                    const f32x16 v = st.vec();
+                    char* const p = shf.img + FAR_SAVE_FEAT + 4 * (32 * t + 4 * h);
+                    *reinterpret_cast<f32x4*>(p) = __builtin_shufflevector(v, v, 0, 1, 2, 3);
+                    *reinterpret_cast<f32x4*>(p + 32) = __builtin_shufflevector(v, v, 4, 5, 6, 7);
+                    *reinterpret_cast<f32x4*>(p + 64) = __builtin_shufflevector(v, v, 8, 9, 10, 11);
+                    *reinterpret_cast<f32x4*>(p + 96) = __builtin_shufflevector(v, v, 12, 13, 14, 15);
+                }
                 if constexpr (S16) {
                     if (a.feat != nullptr) {
                         const int g4 = lane >> 4, n0 = tile * WG_SAMPLES + wave * 32 + (lane & 15);
@@ -1248,61 +1214,8 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         auto reverse = [&](h8(&ih)[16], h8(&il)[16], h8(&oh)[16], h8(&ol)[16], int l) __attribute__((always_inline)) {
             run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ih, il, lane, h, act_of(HS_A1 + l), PhDsig{}, to_regs_keep(KeepAdj{}, oh, ol, HS_DZ + l), no_store);
         };
-        if constexpr (!LEAN) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) sh.frag_load(HS_DZ7 * SLOT_BYTES, s, ah[s], al[s]);
-        }
-        // the zero fragments of the all-far program's discarded passes: two run-time zeros, hi and lo (with one, the first MFMAs of a
-        // group's two accumulators are one expression)
-        [[maybe_unused]] h8 zh[16], zl[16];
-        [[maybe_unused]] auto far_zeros = [&]() {
-            h8 z;
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) z[jj] = (_Float16)0.f;
-            asm volatile("" : "+v"(z));
-            h8 z2 = z;
-            asm volatile("" : "+v"(z2));
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                zh[s] = z;
-                zl[s] = z2;
-            }
-        };
-        if constexpr (LEAN) {
-            // The all-far program whose Jacobian pass multiplies zero fragments: d sdf / d p is a run-time +0 by construction, nothing
-            // reads dz6 .. dz0, and the sweep's 56 products (FAR_REV_TABLE) are discarded like that pass's.
-            // discarded_pass: 56 groups; its first chunk (W7^T, tile 0) was begun by lin8, the chunk needed next is the JACOBIAN PASS's
-            // FIRST CHUNK, 56 chunks on from the sweep's first, and the pass below is untouched.
-            // Every group is one tile of the full sweep -- 16 k-steps onto zeroed accumulators, PH MFMAs per product -- with the zero
-            // fragment as B (two run-time zeros, hi and lo, as in the other passes) and its results sunk: no epilogue, no sigma' from a
-            // stashed a_l, no fragments of dz parked or stashed.  A reverse chunk has no tail, so the held k-step is finite whichever
-            // layer's it is.  mma_held launders its A fragment per group: the disassembly keeps the sweep's 56 x 16 PH MFMAs
-            // (tests/test_far_hold_isa.py).
-            far_zeros();   // (the Jacobian pass below multiplies the same two)
-            f32x16 r1, r2;
-            // the results of MFMAs that run for the dense count.  A single-pass product never touches its second accumulator, which is
-            // then not sunk: its 16 registers of zeros per group cost k_field2_hand_f16<1> 22 more spilled registers, twelve of them
-            // reloaded inside the general program's Jacobian loop (profiles/r14)
-            auto sink = [](const f32x16& c1, const f32x16& c2) {
-                if constexpr (PH == 3)
-                    asm volatile("" ::"v"(c1), "v"(c2));
-                else
-                    asm volatile("" ::"v"(c1));
-            };
-            HeldA held = discarded_pass(std::integral_constant<int, HB_BWD>{}, std::integral_constant<int, FAR_REV_TABLE>{}, [&](auto, const char* buf) {
-                r1 = zero16();
-                r2 = zero16();
-                mma_tile<16, 0, HB_BWD, PH>(ws, buf, zh, zl, r1, r2, lane);
-                sink(r1, r2);
-            });
-            static_for<FAR_REV_TABLE - FAR_TABLE_FETCHED>([&](auto) {
-                r1 = zero16();
-                r2 = zero16();
-                ws.held();
-                mma_held<1, 16, PH>(ws, held, zh, zl, &r1, &r2);
-                sink(r1, r2);
-            });
-        } else {
         reverse(ah, al, bh, bl, 6);   // W7^T -> dz6
         reverse(bh, bl, ah, al, 5);   // W6^T -> dz5
         run_layer_c<8, 16, 1, false, true, HB_BWD, HB_BWD, PH>(ws, ah, al, lane, h, act_of(HS_A1 + 4), PhDsig{},                               // W5^T -> dz4 (kept)
@@ -1322,63 +1235,18 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
         reverse(ah, al, bh, bl, 2);   // W3^T -> dz2
         reverse(bh, bl, ah, al, 1);   // W2^T -> dz1
         reverse(ah, al, bh, bl, 0);   // W1^T -> dz0
-        }   // the real sweep
 
         if ((HN_DBG(a) >> 8) == 7) return true;   // phase timing aid
         // ---- d sdf / d features contracted with the encoding Jacobian, bone by bone: first W0^T dz0 (dz0 is in
         //      bh/bl), then W4[:, 256:]^T dz4 (reloaded into ah/al)
         // G = W0^T dz0 + W4[:, 256:]^T dz4 accumulated per tile (chunks alternate between the two matrices),
         // so that the features and the Jacobian are visited once
-        // (the all-far program without table chunks discards the pass's products and multiplies the zero fragment instead: dz0 and dz4
-        //  are dead behind the reverse sweep, and nothing is reloaded or moved here)
-        if constexpr (!LEAN) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) sh.frag_load(HS_DZ4 * SLOT_BYTES, s, ah[s], al[s]);
         // dz0 (parked in AGPRs by the last reverse layer) is the B operand of 44 chunks: back into VGPRs once, here
 #pragma unroll
         for (int s = 0; s < 16; ++s) asm volatile("" : "+a"(bh[s]), "+a"(bl[s]), "+a"(ah[s]), "+a"(al[s]));
-        }
-        if constexpr (LEAN) {
-            // The all-far program that fetches no table chunk (FAR_JAC_TABLE): the pass's 88 products are discarded, so all but its
-            // first two chunks are neither fetched nor waited for.
-            // discarded_pass: 88 groups; its first chunk is the leftover block's W0 tile, the chunk needed next is COLOUR LIN0's FIRST
-            // CHUNK, 88 chunks on from the pass's first.
-            // Groups (a tile's "dz0" group, then its "dz4" group), accumulators and the sinks of the results are the full stream's.
-            // The B operands are the zero fragment in every group: with dz0 and dz4 they were the last products of the tile that still
-            // switched the matrix pipe on sample-dependent values for nothing.  Two run-time zeros, hi and lo, as in the feature
-            // passes (with one, the first MFMAs of a group's two accumulators are one expression).
-            // No result of the pass is kept.  Every iteration of the bone loop is the same expression on the same operands: mma_held
-            // launders its A fragment per group, and the disassembly keeps 88 x 48 MFMAs (tests/test_far_hold_isa.py).
-            HeldA held;
-            // a tile on the held k-step: its "dz0" group, then its "dz4" group
-            auto held_tile = [&](f32x16& g1, f32x16& g2) {
-                g1 = zero16();
-                g2 = zero16();
-                ws.held();
-                mma_held<1, 16, PJ>(ws, held, zh, zl, &g1, &g2);
-                ws.held();
-                mma_held<1, 16, PJ>(ws, held, zh, zl, &g1, &g2);
-            };
-            {
-                f32x16 L1[2], L2[2];
-                held = discarded_pass(std::integral_constant<int, HB_BWD>{}, std::integral_constant<int, FAR_JAC_TABLE>{}, [&](auto G, const char* buf) {
-                    if constexpr (decltype(G)::value == 0) {
-                        L1[0] = zero16();
-                        L2[0] = zero16();
-                    }
-                    mma_tile<16, 0, HB_BWD, PJ>(ws, buf, zh, zl, L1[0], L2[0], lane);   // the first tile's "dz0" group, then its "dz4" group
-                });
-                held_tile(L1[1], L2[1]);
-                asm volatile("" ::"v"(L1[0]), "v"(L2[0]), "v"(L1[1]), "v"(L2[1]));   // (the results of MFMAs that run for the dense count)
-            }
-#pragma unroll 1
-            for (int b = 0; b < N_BONES; ++b) {
-                f32x16 G1[2], G2[2];
-                held_tile(G1[0], G2[0]);
-                held_tile(G1[1], G2[1]);
-                asm volatile("" ::"v"(G1[0]), "v"(G2[0]), "v"(G1[1]), "v"(G2[1]));
-            }
-        } else {
+        {
             // The leftover block first (2 tiles; register 8 (u & 1) + j of tile u >> 1 <-> bone 8 u + j : (r_1 | r_2) h): its
             // per-bone values are parked in the stash and join the bone's own sums below, so that every bone is visited
             // ONCE (coordinates, d/dq, R_b^T) -- as a block behind the bones it cost a second round over all 21 of them,
@@ -1614,11 +1482,28 @@ __device__ __forceinline__ void field2_hand_body(const Hand2Args& a) {
             a.rgb[3 * n + 1] = rgb[1];
             a.rgb[3 * n + 2] = rgb[2];
         }
+        if constexpr (FAR) {
+            // the far result of the launch, as stored above, for the reuse program (FAR_SAVE; the feature rows: lin8's callback).  No
+            // value of an all-far tile depends on the sample, so lane 0's are every lane's
+            using f32x4 = float __attribute__((ext_vector_type(4)));
+            if (lane == 0) *reinterpret_cast<f32x4*>(shf.img + FAR_SAVE) = f32x4{sdf, rgb[0], rgb[1], rgb[2]};
+        }
         return false;
+        }   // the programs that compute
         };   // program
         if constexpr (FAR_ARM) {
-            const bool out = !far ? program(std::integral_constant<int, 0>{})
-                                  : ((a.far_epilogue != 0 && a.far_stream != 0) ? program(std::integral_constant<int, 2>{}) : program(std::integral_constant<int, 1>{}));
+            // An all-far tile: the workgroup's first one of the launch computes the far result (FAR_ = 1) and, with both switches on,
+            // every later one reuses it.  One workgroup-uniform choice per tile, outside any MFMA stream.
+            const bool reuse = a.far_epilogue != 0 && a.far_stream != 0;
+            bool out;
+            if (!far) {
+                out = program(std::integral_constant<int, 0>{});
+            } else if (reuse && have_far) {
+                out = program(std::integral_constant<int, 2>{});
+            } else {
+                out = program(std::integral_constant<int, 1>{});
+                have_far = reuse;
+            }
             if (out) return;
         } else {
             if (program(std::integral_constant<int, 0>{})) return;

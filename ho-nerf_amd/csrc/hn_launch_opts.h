@@ -25,12 +25,10 @@ struct FieldLaunchOpts {
     // HONERF_FAR_TILES (Hand2Args::far_tiles): 0 = every tile of the hand evaluation kernel runs the general tile program; 1 = all-far
     // tiles run their own (the same bits)
     int far_tiles = 1;
-    // HONERF_FAR_EPILOGUE (Hand2Args::far_epilogue): 1 = the all-far tile program computes the element-wise epilogues of the SDF
-    // network's layers once per row of lanes; 0 = per lane, as the general program does (the same bits)
+    // HONERF_FAR_EPILOGUE (Hand2Args::far_epilogue) and HONERF_FAR_STREAM (Hand2Args::far_stream), both 1: a workgroup computes the far
+    // result in its first all-far tile of a launch and its later all-far tiles reuse it (no weight chunk, no epilogue, the MFMAs on
+    // held operands); either 0 = every all-far tile runs the all-far program that streams every chunk and computes (the same bits)
     int far_epilogue = 1;
-    // HONERF_FAR_STREAM (Hand2Args::far_stream): 1 = the all-far tile program with the shared epilogue neither fetches nor waits for
-    // the weight chunks whose products are 0 * w or discarded (the bone chunks of the three feature passes, the Jacobian pass); 0 =
-    // all-far tiles run the all-far program that streams every chunk, with the per-lane epilogue (the same bits)
     int far_stream = 1;
 };
 

@@ -298,7 +298,7 @@ struct WStream {
         stamp(3);
         return lds + (phase ^ 1) * CHUNK_MAX;
     }
-    // A group of MFMAs that reads NOTHING (the all-far hand program's discarded passes, hn_field2_hand.hip): its A fragments are held
+    // A group of MFMAs that reads NOTHING (the hand kernel's reuse program for all-far tiles, hn_field2_hand.hip): its A fragments are held
     // in registers (mma_held below).  No wait, no barrier and no memory clobber -- nothing lands and nothing is read.  The rule a
     // fetch has to keep is unchanged: it goes into buffer X only behind a barrier that every wave reaches after its last read of X.
     // The stamps alone, so that a timing build still records one chunk start per group.
@@ -656,10 +656,11 @@ __device__ __forceinline__ void mma_chunk(WStream& ws, const char* buf, const h8
 
 // The same group of NT tiles x KS k-steps -- the same 3 NT KS MFMAs in the same order onto the same accumulators -- with ONE k-step's
 // A fragments, [hi | lo] in 8 VGPRs, HELD in registers for every block of the group: no LDS read, no DMA piece.  For groups whose
-// products are +-0 or discarded whatever finite A they multiply (the discarded passes of the all-far hand program).
+// products are +-0 or discarded whatever finite A they multiply (the reuse program of the hand kernel's all-far tiles).
 // A group whose other operands and accumulator seeds do not change from one group to the next is otherwise ONE expression to the
-// compiler -- the MFMA builtin is pure -- and is hoisted out of a loop or merged with its twin: the hi fragment, which the first
-// MFMA of either accumulator chain reads, is laundered per group, so every group is issued.
+// compiler -- the MFMA builtin is pure -- and is hoisted out of a loop or merged with its twin, and so are the tiles of one group
+// whose accumulators start from the same value: the hi fragment, which the first MFMA of either accumulator chain reads, is
+// laundered per tile, so every tile of every group is issued.
 struct HeldA {
     h8 hi, lo;
 };
@@ -674,11 +675,11 @@ template <int NT, int KS, int PASSES = 3, int NX>
 __device__ __forceinline__ void mma_held(WStream& ws, HeldA& w, const h8 (&xh)[NX], const h8 (&xl)[NX], f32x16* c1, f32x16* c2) {
     static_assert(KS <= NX, "k-step range");
     static_assert(!S16 || KS % 2 == 0, "the 16x16x32 shape consumes k-steps in pairs");
-    asm volatile("" : "+v"(w.hi));
     auto slot = [&](auto) { __builtin_amdgcn_sched_barrier(0); };
     static_for<NT * KS>([&](auto S) {
         constexpr int s = decltype(S)::value;
         constexpr int t = s / KS, k = s % KS;
+        if constexpr (k == 0) asm volatile("" : "+v"(w.hi));
         if constexpr (k == 0 && NT > 1) ws.stamp(5);   // (the stamps of mma_chunk; NT == 1: those of mma_tile)
         mma_block<k, 0, PASSES>(w.hi, w.lo, xh, xl, c1[t], c2[t], slot);
     });
@@ -893,16 +894,6 @@ template <typename T>
 struct ph_delay<T, std::void_t<decltype(T::delay)>> {
     static constexpr int value = T::delay;
 };
-// A phase type with `static constexpr bool own_calls = true` runs the 48 calls of a tile epilogue itself (`ph.call<C, FRAGS>(st, pd)`)
-// instead of pair_phase: the shared epilogue of the hand field's all-far tiles (PhFarShared, hn_field2_hand.hip).
-template <typename T, typename = void>
-struct ph_own_calls {
-    static constexpr bool value = false;
-};
-template <typename T>
-struct ph_own_calls<T, std::void_t<decltype(T::own_calls)>> {
-    static constexpr bool value = T::own_calls;
-};
 template <bool FRAGS, typename Ph, typename PD>
 struct Epi {
     static constexpr bool branchy = Ph::branchy;
@@ -912,10 +903,7 @@ struct Epi {
     template <int C>
     __device__ __forceinline__ void call() {
 #if HN_EPI_PAIRS
-        if constexpr (ph_own_calls<Ph>::value)
-            ph.template call<C, FRAGS>(st, pd);
-        else
-            pair_phase<C / 6, C % 6, Ph::kind, FRAGS>(st, pd);
+        pair_phase<C / 6, C % 6, Ph::kind, FRAGS>(st, pd);
 #else
         constexpr int I = C / 3, P = C % 3;
         if constexpr (P < 2)
