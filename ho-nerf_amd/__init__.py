@@ -7,5 +7,6 @@ Import as ``honerf_amd`` (see ../honerf_amd/__init__.py).  Submodules:
   renderer   NeuSRenderer / NeuSRenderer_fitting adapters (utils/renderer.py surface)
   renderer_batch  frame-batched NeuSRenderer_fitting (utils/renderer_batch.py surface)
   fitting    frame-sharded fitting drivers
+  pose_metrics, mesh_distance, alignment   evaluation on the device: pose accuracy, surface distance, Procrustes / ICP alignment
 """
 __version__ = '0.1.0'

@@ -204,6 +204,12 @@ SIGNATURES = {
     'hn_meshdist_closest': (c_i, [c_vp, c_sz, ctypes.c_longlong, c_f, ctypes.c_longlong, c_i, c_f, c_vp, c_f, c_f, c_vp]),
     'hn_mesh_face_areas': (c_i, [c_f, ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, c_f, c_vp]),
     'hn_mesh_sample': (c_i, [c_f, ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong, ctypes.c_uint, c_f, c_vp, c_f, c_vp]),
+    'hn_align_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong]),
+    'hn_align_chunk': (c_i, []),
+    'hn_align_moments': (c_i, [c_f, c_f, c_f, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_sz, c_vp]),
+    'hn_align_solve': (c_i, [c_vp, ctypes.c_longlong, c_i, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'hn_align_apply': (c_i, [c_f, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp, ctypes.c_longlong, c_f, c_vp]),
+    'hn_align_compose': (c_i, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp]),
     'hn_meshcc_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong]),
     'hn_meshcc_measure_workspace_bytes': (c_sz, [ctypes.c_longlong, ctypes.c_longlong]),
     'hn_meshcc_label': (c_i, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),

@@ -176,7 +176,7 @@ def _direction(samples, normals, index):
     return r['dist'].double(), dots.mean()
 
 
-def surface_metrics(pred, gt, n=100_000, taus=(0.005, 0.010), seed=0, samples=None):
+def surface_metrics(pred, gt, n=100_000, taus=(0.005, 0.010), seed=0, samples=None, align=None, icp_iters=30):
     """pred and gt meshes scored against each other -> a dict of Python floats, in the meshes' units.  acc: the distances from n
     samples of pred (seed) to gt; comp: from n samples of gt (seed + 1) to pred.
       chamfer_l1 = (mean acc + mean comp) / 2, chamfer_l2 = mean acc^2 + mean comp^2, hausdorff = max of both maxima,
@@ -184,7 +184,15 @@ def surface_metrics(pred, gt, n=100_000, taus=(0.005, 0.010), seed=0, samples=No
       fscore@tau = 2 p r / (p + r) (0 when p + r = 0), normal_consistency = the mean of both directions' mean |n_sample . n_face|,
       n, pred_area, gt_area.
     Every sum is an fp64 reduction of the device, the same bits on every run.  `samples`: a dict that receives the device's own
-    samples (pred_points, pred_normals, gt_points, gt_normals), for callers that check the metrics."""
+    samples (pred_points, pred_normals, gt_points, gt_normals), for callers that check the metrics.
+
+    align='icp' (rigid) or 'icp+scale' (similarity): the pred mesh is first moved onto gt by `alignment.icp` of its n samples against
+    the gt mesh (`icp_iters` iterations), so that a global pose offset stops dominating a shape score.  The pred SAMPLES are
+    transformed, not redrawn, their normals rotated; comp is measured against the moved pred mesh.  The dict gains `transform` (R
+    [3, 3], s, t as nested lists and floats, float64) and `icp_rms` (the ICP's RMS trace, a list); pred_area stays the unmoved mesh's.
+    None: nothing is aligned."""
+    if align not in (None, 'icp', 'icp+scale'):
+        raise ValueError("surface_metrics: align must be None, 'icp' or 'icp+scale', got %r" % (align,))
     mp, mg = _mesh(pred, 'surface_metrics pred'), _mesh(gt, 'surface_metrics gt')
     n = int(n)
     if n < 1:
@@ -194,7 +202,18 @@ def surface_metrics(pred, gt, n=100_000, taus=(0.005, 0.010), seed=0, samples=No
     gp, _, gn, ga = _sample(mg, n, (int(seed) + 1) % 2 ** 32, 'surface_metrics gt')
     if samples is not None:
         samples.update(pred_points=pp, pred_normals=pn, gt_points=gp, gt_normals=gn)
-    acc, nc_a = _direction(pp, pn, MeshIndex(mg))
+    index_g = MeshIndex(mg)
+    moved = None
+    if align is not None:
+        from . import alignment
+        moved = alignment.icp(pp, index_g, iters=icp_iters, scale=align == 'icp+scale')
+        R, s, t = moved['R'][None].contiguous(), moved['s'][None].contiguous(), moved['t'][None].contiguous()
+        pp = moved['aligned']
+        pn = (pn.double() @ R[0].T).float().contiguous()              # (unit normals: a rotation of 3-vectors, plumbing)
+        mp = _Mesh(alignment._apply(mp.v32[None].contiguous(), R, s, t)[0], mp.t)
+        if samples is not None:
+            samples.update(pred_points=pp, pred_normals=pn)
+    acc, nc_a = _direction(pp, pn, index_g)
     comp, nc_c = _direction(gp, gn, MeshIndex(mp))
     vals = [acc.mean(), comp.mean(), (acc * acc).mean(), (comp * comp).mean(), acc.max(), comp.max(), nc_a, nc_c]
     for t in taus:
@@ -207,4 +226,8 @@ def surface_metrics(pred, gt, n=100_000, taus=(0.005, 0.010), seed=0, samples=No
         p, r = vals[8 + 2 * k] / n, vals[9 + 2 * k] / n
         out['precision@%g' % t], out['recall@%g' % t] = p, r
         out['fscore@%g' % t] = 2.0 * p * r / (p + r) if p + r > 0.0 else 0.0
+    if moved is not None:
+        tr = torch.cat([moved['R'].reshape(-1), moved['s'].reshape(-1), moved['t'].reshape(-1)]).tolist()
+        out['transform'] = dict(R=[tr[0:3], tr[3:6], tr[6:9]], s=tr[9], t=tr[10:13])
+        out['icp_rms'] = [float(x) for x in moved['rms']]
     return out

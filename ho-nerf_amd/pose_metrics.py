@@ -17,6 +17,10 @@ over all pairs of a frame, and the means are accumulated in fp64.
 Arguments are numpy arrays or torch tensors, on either device, float32 or float64; they are moved to the current CUDA device.
 `nearest_distance`, `paired_distance`, `add`, `adds`, `joint_error` and `accel_error` return device tensors; `pose_metrics` and
 `accel_metrics`, the summaries, read everything back once and return numpy arrays and floats.
+
+The benchmarks' aligned numbers (FreiHAND / HO-3D / DexYCB): `pa_joint_error` and `pa_add` score the prediction after a
+similarity Procrustes onto the ground truth (`alignment.procrustes`), `pck_auc` is the PCK curve and its area, `hand_metrics` the
+summary of both, raw and aligned.
 """
 import numpy as np
 import torch
@@ -163,6 +167,110 @@ def joint_error(pred_joints, gt_joints):
     p, g, flat = _clouds(pred_joints, gt_joints, 'pred_joints', 'gt_joints', same_points=True)
     m = _row_mean(_paired(*_pair_inputs(p, g)))
     return m[0] if flat else m
+
+
+def _pa_distances(pred, gt, what_p, what_g):
+    """Per-point distances after the similarity Procrustes of pred onto gt, frame by frame -> (fp32 [F, N], the aligned pred and gt as
+    the kernels saw them (fp32; relative to gt's first point for float64 inputs), was 2-D)."""
+    from .alignment import procrustes
+    p, g, flat = _clouds(pred, gt, what_p, what_g, same_points=True)
+    p32, g32 = _pair_inputs(p, g)
+    aligned = procrustes(p32, g32, scale=True)['aligned']
+    return _paired(aligned, g32), aligned, g32, flat
+
+
+def pa_joint_error(pred_joints, gt_joints):
+    """PA-MPJPE per frame: the mean joint distance after the similarity Procrustes (rotation, scale, translation) of the prediction onto
+    the ground truth: [F, J, 3] x 2 -> float64 [F] on the device (a 0-d tensor for [J, 3] inputs)."""
+    d, _, _, flat = _pa_distances(pred_joints, gt_joints, 'pred_joints', 'gt_joints')
+    m = _row_mean(d)
+    return m[0] if flat else m
+
+
+def pa_add(pred_pts, gt_pts):
+    """`add` after the similarity Procrustes of pred onto gt (PA-MPVPE for hand vertices): [F, N, 3] x 2 -> float64 [F] on the device."""
+    d, _, _, flat = _pa_distances(pred_pts, gt_pts, 'pred_pts', 'gt_pts')
+    m = _row_mean(d)
+    return m[0] if flat else m
+
+
+def _thresholds(lo, hi, steps):
+    lo, hi, steps = float(lo), float(hi), int(steps)
+    if not hi > lo or steps < 2:
+        raise ValueError('pck_auc: thresholds lo = %r, hi = %r, steps = %r: hi > lo and at least 2 steps' % (lo, hi, steps))
+    return np.linspace(lo, hi, steps)
+
+
+def _pck_counts(errors, thr):
+    """errors: a device tensor of any shape, thr float64 numpy [K] -> int64 [K] on the device: the entries <= each threshold."""
+    e = errors.reshape(-1).double()
+    t = torch.from_numpy(thr).to(e.device)
+    counts = torch.zeros(len(thr), dtype=torch.int64, device=e.device)
+    for s in range(0, e.shape[0], 1 << 20):                          # (1M entries x K thresholds of booleans at a time)
+        counts += (e[s:s + (1 << 20), None] <= t[None]).sum(0)
+    return counts
+
+
+def _auc(pck, thr):
+    return float(((pck[1:] + pck[:-1]) * 0.5 * np.diff(thr)).sum() / (thr[-1] - thr[0]))
+
+
+def pck_auc(errors, lo=0.0, hi=0.05, steps=100):
+    """The PCK curve of FreiHAND's evaluation and the area under it: thresholds = linspace(lo, hi, steps), pck[k] = the fraction of ALL
+    entries of `errors` (distances, any shape, metres) <= thresholds[k], auc = the trapezoid sum of pck over the thresholds / (hi -
+    lo).  -> dict(thresholds, pck: float64 numpy [steps]; auc: float; count: int64 numpy [steps]).  The counts are integers: exact."""
+    if isinstance(errors, np.ndarray):
+        errors = torch.from_numpy(np.ascontiguousarray(errors))
+    if not isinstance(errors, torch.Tensor) or errors.dtype not in _FLOATS or errors.numel() == 0:
+        raise ValueError('errors: expected a non-empty float32 or float64 numpy array or torch tensor')
+    thr = _thresholds(lo, hi, steps)
+    e = errors.detach().to(_device())
+    count = _pck_counts(e, thr).cpu().numpy()
+    pck = count / float(e.numel())
+    return dict(thresholds=thr, pck=pck, auc=_auc(pck, thr), count=count)
+
+
+def _fscore_counts(a, b, taus):
+    """a, b fp32 [F, N, 3] / [F, M, 3] -> float64 [2 len(taus), F]: per tau the a points within tau of b, then the b points within tau of a."""
+    da, db = _nearest(a, b), _nearest(b, a)
+    rows = []
+    for t in taus:
+        rows += [(da.double() <= t).sum(1).double(), (db.double() <= t).sum(1).double()]
+    return torch.stack(rows)
+
+
+def hand_metrics(pred_joints, gt_joints, pred_verts=None, gt_verts=None, lo=0.0, hi=0.05, steps=100):
+    """The hand benchmarks' table for F frames: mpjpe and pa_mpjpe (the mean over frames and joints of the joint distance, raw and after
+    the per-frame similarity Procrustes), auc and pa_auc (`pck_auc` of all F x J joint distances, raw and aligned), and with vertices
+    [F, V, 3] mpvpe, pa_mpvpe, f5, f15: the mean over the frames of the F-score at 5 mm and 15 mm between the ALIGNED predicted
+    vertices and the ground truth's as point sets (`nearest_distance` both ways: precision = the share of aligned vertices within tau of
+    a gt vertex, recall the other way round, 2 p r / (p + r), 0 when both are 0).  Metres; Python floats; one read-back."""
+    if (pred_verts is None) != (gt_verts is None):
+        raise ValueError('pred_verts and gt_verts: pass both or neither')
+    thr = _thresholds(lo, hi, steps)
+    K = len(thr)
+    pj, gj, _ = _clouds(pred_joints, gt_joints, 'pred_joints', 'gt_joints', same_points=True)
+    d_raw = _paired(*_pair_inputs(pj, gj))
+    d_pa = _pa_distances(pj, gj, 'pred_joints', 'gt_joints')[0]
+    F = d_raw.shape[0]
+    parts = [_row_mean(d_raw).mean()[None], _row_mean(d_pa).mean()[None], _pck_counts(d_raw, thr).double(), _pck_counts(d_pa, thr).double()]
+    if pred_verts is not None:
+        pv, gv, _ = _clouds(pred_verts, gt_verts, 'pred_verts', 'gt_verts', same_points=True)
+        if pv.shape[0] != F:
+            raise ValueError('pred_verts has %d frames and pred_joints has %d' % (pv.shape[0], F))
+        v_raw = _paired(*_pair_inputs(pv, gv))
+        v_pa, aligned, g32, _ = _pa_distances(pv, gv, 'pred_verts', 'gt_verts')
+        parts += [_row_mean(v_raw).mean()[None], _row_mean(v_pa).mean()[None], _fscore_counts(aligned, g32, (0.005, 0.015)).reshape(-1)]
+    host = torch.cat(parts).cpu().numpy()                             # the one read-back
+    n = float(d_raw.numel())
+    out = dict(mpjpe=float(host[0]), pa_mpjpe=float(host[1]), auc=_auc(host[2:2 + K] / n, thr), pa_auc=_auc(host[2 + K:2 + 2 * K] / n, thr))
+    if pred_verts is not None:
+        o = 2 + 2 * K
+        V = float(v_raw.shape[1])
+        c = host[o + 2:].reshape(4, F) / V
+        fs = lambda p, r: float(np.where(p + r > 0, 2.0 * p * r / np.where(p + r > 0, p + r, 1.0), 0.0).mean())
+        out.update(mpvpe=float(host[o]), pa_mpvpe=float(host[o + 1]), f5=fs(c[0], c[1]), f15=fs(c[2], c[3]))
+    return out
 
 
 def _vis_keep(vis, n):

@@ -944,6 +944,39 @@ int hn_meshcc_compact_emit(const void* vertices, int vertices_f64, long long n_v
                            size_t workspace_bytes, long long n_verts_out, long long n_tris_out, void* vertices_out, long long* triangles_out,
                            int* vertex_map, int* face_map, hn_stream_t stream);
 
+/* ---- rigid and similarity alignment of paired point clouds (hn_align.hip): Procrustes, the step of an ICP -------------------------------
+ * Replaces what an evaluation otherwise leaves the device for: scipy.linalg.orthogonal_procrustes / trimesh.registration.procrustes
+ * (moments + solve), a transform applied to a cloud (apply), trimesh.registration.icp's accumulated transform (compose).  DESIGN.md
+ * 3.28 is the contract; tests/alignment_cases.py restates it in float64.  The transform is x -> s R x + t, R [3, 3] row-major.
+ *   hn_align_workspace_bytes: the workspace of one hn_align_moments call (0 for counts it refuses);
+ *   hn_align_chunk: the points one wave sums (the tree's chunk: honerf_amd.alignment.CHUNK);
+ *   hn_align_moments: src, dst [F, N, 3] fp32, weight [F, N] fp32 or NULL (all ones; weights are taken as they are: a caller keeps
+ *     them >= 0) -> moments [F, 18] fp64: W = sum w, ca[3] = sum w a / W, cb[3], H[9] = sum w (b - cb)(a - ca)^T row-major, va = sum w
+ *     |a - ca|^2, vb (a = src, b = dst; W = 0: centroids and moments 0).  Two passes: the centroids, then differences from them in
+ *     fp64.  The summation tree is fixed by N: chunks of 1024 points, lane l of a wave adds points l, l + 64, ... of its chunk, an xor
+ *     butterfly (32 .. 1) joins the lanes, a frame's chunks are added in order.  The same bits for a frame alone and among others, for
+ *     NULL and explicit ones, on every run; no atomics;
+ *   hn_align_solve: moments -> R [F, 3, 3], s [F], t [F, 3] fp64, rank [F] int32: the proper rotation (det +1) that minimises
+ *     sum w |s R a + t - b|^2, from Horn's symmetric 4 x 4 matrix (linear in H) by cyclic Jacobi rotations, at most 24 sweeps, one
+ *     thread per frame; s = sum_ik R_ik H_ik / va when with_scale (0 at least; 1 when va = 0), else 1; t = cb - s R ca.  With l1 >= l2 the
+ *     two largest eigenvalues: rank 0 when W = 0 or l1 <= 1e-10 sqrt(va vb) (coincident points: R = I); rank 1 when l1 - l2 <= 1e-10
+ *     l1 (collinear points, or a mirror image whose two smaller singular values agree: of the optimal rotations the one with the
+ *     smallest angle); else rank 3.  Never NaN for finite moments;
+ *   hn_align_apply: pts [F, N, 3] fp32 -> out = (float)(s ((R0 x + R1 y) + R2 z) + t) per row, in fp64, rounded once; n_transforms is F
+ *     or 1 (one transform for every frame);
+ *   hn_align_compose: (R2, s2, t2) o (R1, s1, t1) = (R2 R1, s2 s1, s2 R2 t1 + t2) per frame in fp64; the outputs may be either input.
+ * Nothing allocates or synchronises.  A NULL pointer (but weight), a count < 1, frames x points >= 2^31 - 1024 or a workspace that is
+ * too small is HN_EINVAL with a message, before anything is launched. */
+size_t hn_align_workspace_bytes(long long n_frames, long long n_points);
+int hn_align_chunk(void);
+int hn_align_moments(const float* src, const float* dst, const float* weight, long long n_frames, long long n_points, double* moments, void* workspace,
+                     size_t workspace_bytes, hn_stream_t stream);
+int hn_align_solve(const double* moments, long long n_frames, int with_scale, double* R, double* s, double* t, int* rank, hn_stream_t stream);
+int hn_align_apply(const float* pts, long long n_frames, long long n_points, const double* R, const double* s, const double* t, long long n_transforms,
+                   float* out, hn_stream_t stream);
+int hn_align_compose(const double* R2, const double* s2, const double* t2, const double* R1, const double* s1, const double* t1, long long n_frames,
+                     double* R, double* s, double* t, hn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

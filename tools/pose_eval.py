@@ -6,7 +6,9 @@ honerf_amd.pose_metrics.pose_metrics call on the current GPU and prints the refe
     obj_name <class> has <n> frames
     init joint: .., ours joint: .., init ad: .., init add: .., init adds: .., ours ad: .., ours add: .., ours adds: ..
 (joint and ad: mean, mm; add and adds: frames under 15 mm, %).  Without --init the init columns are left out; a class without frames
-prints its first line only.  --init DIR holds the initial estimates as the reference reads them:
+prints its first line only.  --aligned appends the Procrustes-aligned columns of the hand benchmarks (honerf_amd.pose_metrics.hand_metrics
+on the joints): `pa joint` (PA-MPJPE, mm), `auc` and `pa auc` (the area under the PCK curve over 0 .. 50 mm, raw and aligned), per
+method.  --init DIR holds the initial estimates as the reference reads them:
 DIR/<person>_<object>/<sequence>/pred_joint3d_<n>view/<id>.pickle (key pred_joint_3d) and pred_objpose_<n>view/<id>.txt (a 4 x 4).
 
 The object model of <object> is MODELS/<object>_cppose/<object>_ours.ply or .npy, its vertices times --model-scale (the reference's
@@ -18,7 +20,7 @@ exists are read from 12/../pose_12, 123/../pose_4 and 1234/../pose_4, and the jo
 three are printed, after the number of frames:
     acc_list_1_3_j: .., acc_list_1_3_v: .., acc_list_123_j: .., acc_list_123_v: .., acc_list_1234_j: .., acc_list_1234_v: ..
 
-    python tools/pose_eval.py BASE --view-num 8 --fit-type 12 --models DIR [--init DIR] [--classes bean box cup meat] [--accel]
+    python tools/pose_eval.py BASE --view-num 8 --fit-type 12 --models DIR [--init DIR] [--classes bean box cup meat] [--aligned] [--accel]
 """
 import argparse
 import os
@@ -57,11 +59,11 @@ def read_init(init, obj_name, frame_name, view_num, cid):
 
 def run_pose(args):
     from honerf_amd import harness
-    from honerf_amd.pose_metrics import pose_metrics
+    from honerf_amd.pose_metrics import hand_metrics, pose_metrics
     type_path = os.path.join(args.base, 'view_' + args.view_num, args.fit_type)
     for test_obj in args.classes:
         cnum = 0
-        sums = {m: dict(joint=0.0, ad=0.0, add=0, adds=0) for m in ('ours', 'init')}
+        sums = {m: dict(joint=0.0, ad=0.0, add=0, adds=0, pa=0.0, auc=0.0, pa_auc=0.0) for m in ('ours', 'init')}
         for obj_name in sorted(os.listdir(type_path)) if os.path.isdir(type_path) else []:
             if test_obj not in obj_name:
                 continue
@@ -88,6 +90,12 @@ def run_pose(args):
                     s['ad'] += float(r['ad'].sum())
                     s['add'] += int(r['add_ok'].sum())
                     s['adds'] += int(r['adds_ok'].sum())
+                if args.aligned:                                       # (frame-weighted: every frame has the same 21 joints)
+                    gt_j = stack(poses, 'gt_')['joint3d']
+                    for name, js in [('ours', stack(poses, 'pred_')['joint3d'])] + ([('init', stack(inits, 'init_')['joint3d'])] if args.init else []):
+                        h = hand_metrics(js, gt_j)
+                        for k, key in (('pa', 'pa_mpjpe'), ('auc', 'auc'), ('pa_auc', 'pa_auc')):
+                            sums[name][k] += h[key] * len(poses)
                 cnum += len(poses)
         print('obj_name %s has %d frames' % (test_obj, cnum))
         if not cnum:
@@ -101,6 +109,10 @@ def run_pose(args):
                   'ours adds: %.2lf' % (ij, oj, ia, idd, ids, oa, odd, ods))
         else:
             print('ours joint: %.2lf, ours ad: %.2lf, ours add: %.2lf, ours adds: %.2lf' % (oj, oa, odd, ods))
+        if args.aligned:
+            for name in ('init', 'ours') if args.init else ('ours',):
+                s = sums[name]
+                print('%s pa joint: %.2lf, %s auc: %.3lf, %s pa auc: %.3lf' % (name, s['pa'] / cnum * 1000, name, s['auc'] / cnum, name, s['pa_auc'] / cnum))
     return 0
 
 
@@ -151,6 +163,7 @@ def main():
     ap.add_argument('--init', default=None, help="the reference's ./data/catch_sequence/test")
     ap.add_argument('--classes', nargs='+', default=CLASSES)
     ap.add_argument('--threshold', type=float, default=0.015)
+    ap.add_argument('--aligned', action='store_true', help='add the Procrustes-aligned joint error and the PCK AUCs, raw and aligned')
     ap.add_argument('--accel', action='store_true', help='the acceleration errors of analys_acc_err.py instead')
     ap.add_argument('--max-frame', type=int, default=2000, help='--accel: frame ids 0 .. max-1 are looked for (the reference: 2000)')
     args = ap.parse_args()
