@@ -169,6 +169,15 @@ SIGNATURES = {
     'hn_mcubes_workspace_bytes': (c_sz, [c_i, c_i, c_i]),
     'hn_mcubes_count': (c_i, [c_f, c_i, c_i, c_i, c_fl, c_vp, c_vp, c_sz, c_vp]),
     'hn_mcubes_emit': (c_i, [c_f, c_i, c_i, c_i, c_fl, c_vp, c_sz, ctypes.c_longlong, ctypes.c_longlong, c_f, c_vp, c_vp]),
+    'hn_mcs_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i, ctypes.c_longlong]),
+    'hn_mcs_lattice': (c_i, [c_i, c_i, c_i, c_i, c_vp, c_vp]),
+    'hn_mcs_classify': (c_i, [c_f, c_i, c_i, c_i, c_i, c_fl, c_fl, c_vp, c_vp]),
+    'hn_mcs_compact': (c_i, [c_vp, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'hn_mcs_brick_points': (c_i, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_i, c_i, c_i, c_i, c_vp, c_vp]),
+    'hn_mcs_leaks': (c_i, [c_f, c_vp, c_vp, ctypes.c_longlong, c_i, c_i, c_i, c_i, c_fl, c_vp, c_vp, c_vp]),
+    'hn_mcs_count': (c_i, [c_f, c_vp, ctypes.c_longlong, c_i, c_i, c_i, c_i, c_fl, c_vp, c_vp, c_sz, c_vp]),
+    'hn_mcs_emit': (c_i, [c_f, c_vp, c_vp, ctypes.c_longlong, c_i, c_i, c_i, c_i, c_fl, c_vp, c_sz, ctypes.c_longlong, ctypes.c_longlong,
+                          c_f, c_vp, c_vp, c_vp, c_vp]),
     'hn_voxelize_workspace_bytes': (c_sz, [ctypes.c_longlong]),
     'hn_voxelize_count': (c_i, [c_vp, ctypes.c_longlong, c_db, ctypes.POINTER(ctypes.c_longlong), c_vp, c_sz, c_vp]),
     'hn_voxelize_emit': (c_i, [c_vp, ctypes.c_longlong, c_db, c_vp, c_sz, ctypes.c_longlong, c_vp, c_vp]),

@@ -149,6 +149,36 @@ def _mesh(volume_fn, threshold, resolution, b_min_np, b_max_np, mesher):
     return _to_world(v.cpu().numpy().astype(np.float64), resolution, b_min_np, b_max_np), t.cpu().numpy()
 
 
+def _mesh_sparse(sdf_at, bound_min, bound_max, resolution, threshold, block, lipschitz, grow, return_info):
+    """extract_geometry(..., mesher='sparse'): the mesh of mesher='native', bit for bit, from field values in a band of blocks around
+    the level set (honerf_amd.mesh.marching_cubes_sparse).  sdf_at(pts [n, 3] device, world) -> values [n]: what _volume asks of the
+    field.  The grid is _grid_points' (the same CPU linspace axes, gathered per index).
+
+    reach = lipschitz x half the world diagonal of a block: a level-set point inside a block is at most half a diagonal from the
+    nearest corner, so with a field whose gradient norm is <= lipschitz every block the surface passes through is a candidate before
+    growth starts.  lipschitz cannot be checked from here: the default 1.0 ASSUMES that the eikonal term of training has done its
+    work (DESIGN.md 3.29).  Growth repairs a band that is too thin wherever the missed surface is connected to a found one;
+    lipschitz=0 seeds from sign changes at block corners alone and lets growth follow the surface (the thinnest band; it misses
+    components that straddle no block corner: floaters)."""
+    from .mesh import marching_cubes_sparse
+    dev = torch.device('cuda')
+    res = int(resolution)
+    bmin = torch.as_tensor(bound_min, dtype=torch.float32).reshape(3).cpu()
+    bmax = torch.as_tensor(bound_max, dtype=torch.float32).reshape(3).cpu()
+    ax = [torch.linspace(float(bmin[i]), float(bmax[i]), res).to(dev) for i in range(3)]
+    cell = (bmax.double() - bmin.double()) / (res - 1.0)
+    reach = float(lipschitz) * 0.5 * int(block) * float(cell.norm())
+
+    def values_at(idx):
+        i = idx.long()
+        pts = torch.stack([ax[0][i[:, 0]], ax[1][i[:, 1]], ax[2][i[:, 2]]], -1).contiguous()
+        with torch.no_grad():
+            return sdf_at(pts).reshape(-1)
+    v, t, info = marching_cubes_sparse(values_at, (res, res, res), threshold, block=block, reach=reach, grow=grow)
+    out = (_to_world(v.cpu().numpy().astype(np.float64), resolution, bmin.numpy(), bmax.numpy()), t.cpu().numpy())
+    return out + (info,) if return_info else out
+
+
 def _wants_grad(*xs):
     return torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.requires_grad for x in xs)
 
@@ -363,12 +393,18 @@ class NeuSRenderer:
         in 64^3 host chunks, here the whole grid is one hn_field_sdf launch."""
         return self._volume(bound_min, bound_max, resolution, bt_inv, T_pose_21).cpu().numpy()
 
-    def extract_geometry(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, threshold=0.0, *, mesher=None):
+    def extract_geometry(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, threshold=0.0, *, mesher=None, block=8,
+                         lipschitz=1.0, grow=True, return_info=False):
         """utils/renderer.py:260-284 -> (vertices, triangles).  mesher=None: PyMCubes, as the reference; 'native': the device
-        mesher (honerf_amd.mesh) on the same volume."""
+        mesher (honerf_amd.mesh) on the same volume; 'sparse': the same mesh from field values near the surface only (_mesh_sparse:
+        block, lipschitz, grow; return_info appends marching_cubes_sparse's info dict).  lipschitz is an assumption on the field."""
         _, bmin, bmax = _grid_points(bound_min, bound_max, 2, torch.device('cpu'))
+        if mesher == 'sparse':
+            field = self.field()
+            return _mesh_sparse(lambda pts: field.sdf(pts, bt_inv, T_pose_21), bound_min, bound_max, resolution, threshold, block,
+                                lipschitz, grow, return_info)
         if mesher not in (None, 'native'):
-            raise ValueError("extract_geometry: mesher must be None (PyMCubes) or 'native', got %r" % (mesher,))
+            raise ValueError("extract_geometry: mesher must be None (PyMCubes), 'native' or 'sparse', got %r" % (mesher,))
         return _mesh(lambda: self._volume(bound_min, bound_max, resolution, bt_inv, T_pose_21), threshold, resolution, bmin, bmax,
                      mesher)
 
@@ -628,10 +664,9 @@ class NeuSRenderer_fitting:
         o' = Ro (p - To) first (:550-552)."""
         return self._volume(bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type).cpu().numpy()
 
-    def _volume(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type):
-        """extract_fields' volume as a device tensor [res,res,res]."""
-        dev = torch.device('cuda')
-        pts, _, _ = _grid_points(bound_min, bound_max, resolution, dev)
+    def _sdf_at(self, pts, bt_inv, T_pose_21, Ro, To, get_type):
+        """The field of extract_fields at world points pts [n, 3] (device, contiguous) -> [n] values."""
+        dev = pts.device
         hand, obj = self.fields()
         with torch.no_grad():
             if get_type == 'hand':
@@ -643,14 +678,24 @@ class NeuSRenderer_fitting:
                 _lib.check(self.lib.hn_obj_local_fwd(_lib.ptr(pts), _lib.ptr(pts), _lib.ptr(Ro_), _lib.ptr(To_), 1, pts.shape[0],
                                                      _lib.ptr(local), _lib.ptr(dummy), _lib.stream_ptr()), 'hn_obj_local_fwd')
                 val = obj.sdf(local)
-        return val.reshape(resolution, resolution, resolution)
+        return val
 
-    def extract_geometry(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type, threshold=0.0, *, mesher=None):
+    def _volume(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type):
+        """extract_fields' volume as a device tensor [res,res,res]."""
+        pts, _, _ = _grid_points(bound_min, bound_max, resolution, torch.device('cuda'))
+        return self._sdf_at(pts, bt_inv, T_pose_21, Ro, To, get_type).reshape(resolution, resolution, resolution)
+
+    def extract_geometry(self, bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type, threshold=0.0, *, mesher=None,
+                         block=8, lipschitz=1.0, grow=True, return_info=False):
         """utils/renderer.py:537-564 -> (vertices, triangles).  mesher=None: PyMCubes, as the reference; 'native': the device
-        mesher (honerf_amd.mesh) on the same volume."""
+        mesher (honerf_amd.mesh) on the same volume; 'sparse': the same mesh from field values near the surface only (_mesh_sparse:
+        block, lipschitz, grow; return_info appends marching_cubes_sparse's info dict).  lipschitz is an assumption on the field."""
         _, bmin, bmax = _grid_points(bound_min, bound_max, 2, torch.device('cpu'))
+        if mesher == 'sparse':
+            return _mesh_sparse(lambda pts: self._sdf_at(pts, bt_inv, T_pose_21, Ro, To, get_type), bound_min, bound_max, resolution,
+                                threshold, block, lipschitz, grow, return_info)
         if mesher not in (None, 'native'):
-            raise ValueError("extract_geometry: mesher must be None (PyMCubes) or 'native', got %r" % (mesher,))
+            raise ValueError("extract_geometry: mesher must be None (PyMCubes), 'native' or 'sparse', got %r" % (mesher,))
         return _mesh(lambda: self._volume(bound_min, bound_max, resolution, bt_inv, T_pose_21, Ro, To, get_type), threshold, resolution,
                      bmin, bmax, mesher)
 

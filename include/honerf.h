@@ -707,6 +707,49 @@ int hn_mcubes_count(const float* volume, int nx, int ny, int nz, float threshold
 int hn_mcubes_emit(const float* volume, int nx, int ny, int nz, float threshold, void* workspace, size_t workspace_bytes, long long n_verts,
                    long long n_tris, float* vertices, long long* triangles, hn_stream_t stream);
 
+/* ---- narrow-band marching cubes (hn_mcubes_sparse.hip): the mesh of hn_mcubes_*, bit for bit, from values near the level set only --
+ * The caller owns the field: these calls say where values are needed (int32 grid indices [n, 3]), take them back, and mesh them.
+ * Grid (nx, ny, nz), every dim in [2, 2048]; `block` = b = 4 or 8 cells.  An axis of n points has ceil((n - 1) / b) blocks; block i
+ * covers the cells between points i b and min((i + 1) b, n - 1) (the last may be shorter).  Block ids are linear, x slowest.
+ * A brick is the (b + 1)^3 values of one block, local index (lx (b + 1) + ly)(b + 1) + lz: its points and the apron on its +x, +y, +z
+ * faces; entries beyond the grid are invalid and never read.  Grid point g belongs to block min(g / b, nb - 1) per axis (local index
+ * < b, and the grid's last layer to the last block); the owner of a point owns its +x, +y, +z edges, a cell belongs to the block that
+ * covers it.  No float is accumulated and every offset comes from an integer scan: two runs give the same bits.
+ *   hn_mcs_workspace_bytes: the workspace of hn_mcs_compact (n_slots = 0 suffices) and of hn_mcs_count / hn_mcs_emit on n_slots bricks
+ *     (0 for dims, block or n_slots the mesher refuses);
+ *   hn_mcs_lattice: indices [(nbx + 1)(nby + 1)(nbz + 1), 3] of the block corners, min(i b, n - 1) per axis;
+ *   hn_mcs_classify: lattice_values in that order -> mask [blocks] uint8: 1 where the 8 corners do not agree on value < threshold (the
+ *     inside test of hn_mcubes) or some corner has |value - threshold| <= reach (fp32; reach >= 0);
+ *   hn_mcs_compact: mask -> list (capacity: blocks) = the ascending ids of the marked blocks, table [blocks] = block -> slot in the
+ *     list (-1 where unmarked), total [1] int64 DEVICE (the caller reads it back, 8 bytes);
+ *   hn_mcs_brick_points: indices [(slot_end - slot_begin)(b + 1)^3, 3] of the bricks of list[slot_begin .. slot_end); an invalid entry
+ *     repeats the brick's last valid index of that axis;
+ *   hn_mcs_leaks: bricks [n_slots, (b + 1)^3] of list[0 .. n_slots), table of the same compaction.  For every crossing grid edge on a
+ *     brick's boundary (faces, edges, corners of the block) every block that contains the edge and is not in the table is marked in
+ *     the mask; added [1] int64 DEVICE = the blocks marked and not in the table;
+ *   hn_mcs_count: totals [2] int64 DEVICE = {V, T}; the workspace keeps the offsets the emit call needs;
+ *   hn_mcs_emit: on the workspace of the count call with the same arguments (same stream; V, T < 2^31) -> vertices [V, 3] fp32 at
+ *     v0 + t (v1 - v0), t = (threshold - v0) / (v1 - v0), in global index space (the expression of hn_mcubes_emit on the same operands),
+ *     vertex_keys [V] int64 = 3 (linear index of the owning grid point) + axis, triangles [T, 3] int64 oriented as hn_mcubes_emit's,
+ *     triangle_keys [T] int64 = 8 (linear index of the cell) + place in the table; "linear" is the dense grid's, x slowest.  Both come
+ *     in brick-major order; sorted by key (and the triangles' indices remapped) they are hn_mcubes_emit's arrays.  A triangle whose
+ *     vertex is owned by a block outside the table carries -1 there: only when leaks were left. */
+size_t hn_mcs_workspace_bytes(int nx, int ny, int nz, int block, long long n_slots);
+int hn_mcs_lattice(int nx, int ny, int nz, int block, int* indices, hn_stream_t stream);
+int hn_mcs_classify(const float* lattice_values, int nx, int ny, int nz, int block, float threshold, float reach, unsigned char* mask,
+                    hn_stream_t stream);
+int hn_mcs_compact(const unsigned char* mask, int nx, int ny, int nz, int block, int* list, int* table, long long* total, void* workspace,
+                   size_t workspace_bytes, hn_stream_t stream);
+int hn_mcs_brick_points(const int* list, long long slot_begin, long long slot_end, int nx, int ny, int nz, int block, int* indices,
+                        hn_stream_t stream);
+int hn_mcs_leaks(const float* bricks, const int* list, const int* table, long long n_slots, int nx, int ny, int nz, int block, float threshold,
+                 unsigned char* mask, long long* added, hn_stream_t stream);
+int hn_mcs_count(const float* bricks, const int* list, long long n_slots, int nx, int ny, int nz, int block, float threshold, long long* totals,
+                 void* workspace, size_t workspace_bytes, hn_stream_t stream);
+int hn_mcs_emit(const float* bricks, const int* list, const int* table, long long n_slots, int nx, int ny, int nz, int block, float threshold,
+                void* workspace, size_t workspace_bytes, long long n_verts, long long n_tris, float* vertices, long long* vertex_keys,
+                long long* triangles, long long* triangle_keys, hn_stream_t stream);
+
 /* ---- hand-object interaction (hn_interact.hip): what analys_results/analys_interaction.py:14-19 and :44-55 ask trimesh for -----
  * Meshes are rows of 9 coordinates per triangle (a, b, c), world metres.
  * Voxelization (Trimesh.voxelized(pitch), subdivide, max_iter 10), fp64: a triangle with an edge length sqrt((dx^2 + dy^2) + dz^2)
